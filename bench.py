@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — RTjpeg decode throughput on MI355X (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config frames1080|streams4k|mixed|dv]
+    python bench.py --gpus N --steps K --warmup W [--config frames1080|streams4k|mixed|dv] [--full] [--dump-outputs DIR]
+
+A plain frames1080 run does only what its headline needs: set up, W warm-up steps, K timed steps, the result line.
+`--full` adds everything else it measures or checks (parity against the CPU decoder, the CPU baselines, end to end,
+the copy ceiling, by_batch, stress_amp64); those fields appear in the line only then.  The other configurations
+run as they always did, with or without `--full`.
+`--dump-outputs DIR` (frames1080) writes what the last timed step decoded, as float32 .npy files under DIR: a fixed,
+seeded sample of whole pictures, one file per plane, named by the picture's index (dump_outputs()).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process starts the N ranks itself (one process per
 GPU, `python -m torch.distributed.run`, rendezvous on 127.0.0.1) before anything touches a GPU, passes rank 0's
@@ -28,19 +35,20 @@ Workloads (`config.workload` in the output names the one that ran):
 One process per GPU.  No data-path collective: RCCL carries the barrier and the final (frames, pixels,
 mismatches, max elapsed) reduction only.
 
-Rank 0 prints ONE JSON line: the contract fields plus
+Rank 0 prints ONE JSON line: the contract fields plus (the ones marked [full] only with --full)
   "roofline":      dominant kernel of the path, algorithmic bytes / its HIP-event time vs HBM peak; `traffic` = HBM
                    bytes per launch from the committed PMC profile, only while that profile was taken from the same
                    kernel sources (else null)
   "roofline_valu": the same kernel against the vector-issue roof: instructions per launch (PMC) x measured cost per
                    instruction / measured time
-  "cpu_baseline":  the reference's lib/RTjpeg.c (oracle/_ref, kind "reference") or the oracle port, one thread, timed
+  "cpu_baseline":  [full] the reference's lib/RTjpeg.c (oracle/_ref, kind "reference") or the oracle port, one thread, timed
                    on this box (rank 0's host, whatever N) on a bounded sample of the same packets;
                    "cpu_baseline_all_cores": one decoder per core
-  "parity_checked" / "parity_mismatches": frames of this run compared with the CPU decoder: EVERY rank copies a sample
+  "parity_checked" / "parity_mismatches": [full] frames of this run compared with the CPU decoder: EVERY rank copies a sample
                    of its own output to the host, has its own CPU processes decode the same packets and feeds the counts
                    into the one reduction of the path (parity_checked = N x sample)
-  "by_batch":      (N = 1) the same step at 256 / 1024 / 4096 frames per launch next to the default 16384
+  "by_batch":      [full] (N = 1) the same step at 256 / 1024 / 4096 frames per launch next to the default 16384
+  "end_to_end", "copy_ceiling_gbs", "stress_amp64": [full] (N = 1, see main())
 The process exits non-zero when a compared frame differs.
 """
 import argparse
@@ -89,7 +97,16 @@ def parse():
     ap.add_argument("--no-sweep", action="store_true", help="skip the batch-size sweep (by_batch)")
     ap.add_argument("--selftest-ranks", action="store_true",
                     help="no GPU work: every rank reports a dummy shard through the same reduction (launcher test)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="frames1080: also run what is not the headline (parity against the CPU decoder, CPU baselines, end "
+                         "to end, copy ceiling, by_batch, stress_amp64); the --no-* switches above act only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="frames1080: write a fixed, seeded sample of the pictures the last timed step decoded to DIR as "
+                         "float32 .npy files")
+    a = ap.parse_args()
+    if a.dump_outputs and a.config != "frames1080":
+        ap.error("--dump-outputs is implemented for --config frames1080 only")
+    return a
 
 
 # --------------------------------------------------------------------------- rank launcher
@@ -244,6 +261,31 @@ def pmc_profile():
     return tj
 
 
+# --------------------------------------------------------------------------- outputs for comparison between builds
+DUMP_BYTES = 60 << 20  # --dump-outputs writes at most this much float32
+DUMP_PICTURES = 4
+DUMP_SEED = 20240229  # which pictures are dumped: fixed, so two builds dump the same ones for the same arguments
+
+
+def dump_outputs(path, dev, d_out, n, w, h, stride):
+    """--dump-outputs: what the caller of the path receives is `n` YUV420 pictures in d_out (one every `stride` bytes).
+    Up to DUMP_PICTURES of them, chosen by DUMP_SEED, are written as float32 arrays, one file per plane:
+    pic<index>_y.npy (h x w), pic<index>_u.npy and pic<index>_v.npy (h/2 x w/2).  Pictures too large for DUMP_BYTES
+    keep their top rows only."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    ys, cs = w * h, (w // 2) * (h // 2)
+    k = max(1, min(DUMP_PICTURES, n, DUMP_BYTES // (4 * (ys + 2 * cs))))
+    rows = min(h, (DUMP_BYTES // (4 * k)) // (w + w // 2)) & ~1  # luma rows kept (and half as many chroma rows)
+    for i in sorted(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False).tolist()):
+        pic = dev.d2h(d_out, ys + 2 * cs, offset=i * stride)
+        planes = {"y": pic[:ys].reshape(h, w)[:rows],
+                  "u": pic[ys:ys + cs].reshape(h // 2, w // 2)[:rows // 2],
+                  "v": pic[ys + cs:].reshape(h // 2, w // 2)[:rows // 2]}
+        for name, p in planes.items():
+            np.save(os.path.join(path, f"pic{i:05d}_{name}.npy"), p.astype(np.float32))
+
+
 # --------------------------------------------------------------------------- workloads
 def run_frames(a, dev, rank, n, amp, steps, warmup, barrier, sync_all, timed_unprofiled=False):
     """The resident-batch workload: returns everything rank 0 needs for its line.
@@ -380,12 +422,14 @@ def main():
     n = a.frames or 16384
     r = run_frames(a, dev, rank, n, a.amp, a.steps, a.warmup, barrier, sync_all)
     plan, info, fsz = r["plan"], r["info"], r["fsz"]
-
-    # parity, on EVERY rank: a sample of this rank's own output goes to the host and is compared with what CPU
-    # decoders (processes of this rank, its share of the host's cores) make of the same packets
     pad = int(os.environ.get("MI_RTJ_BENCH_PAD", "0"))
+    if a.dump_outputs and rank == 0:  # before anything else writes to d_out (copy_ceiling does)
+        dump_outputs(a.dump_outputs, dev, r["d_out"], n, w, h, fsz + pad)
+
+    # parity (--full), on EVERY rank: a sample of this rank's own output goes to the host and is compared with what CPU
+    # decoders (processes of this rank, its share of the host's cores) make of the same packets
     pkts, checked, my_mism = [], 0, 0
-    if not a.no_cpu:
+    if a.full and not a.no_cpu:
         ns = min(n, max(32, a.verify_frames if a.verify_frames else (256 if world == 1 else 64)))
         pkts = [dev.d2h(r["d_st"], int(r["pl"][i]), offset=int(r["po"][i])) for i in range(ns)]
         gpu_digests = [hashlib.sha256(dev.d2h(r["d_out"], fsz, offset=i * (fsz + pad)).tobytes()).hexdigest()[:32]
@@ -485,7 +529,7 @@ def main():
                         "measured: the share of the 2.4-cycle issue roof the kernel reaches; frac_of_expensive_rate = "
                         "floor_ms_all_mixed / measured: nearly all of k_decode's instructions are of the expensive class "
                         "(its transform runs two values to a register), so this is the roof it sits under"}
-        if not a.no_cpu:
+        if a.full and not a.no_cpu:
             # the CPU baseline: rank 0's host, for any N (the other ranks wait at the barrier below, the host is idle)
             one, allc = cpu_timed_legs(pkts, w, h, a.cpu_seconds)
             out["cpu_baseline"] = one
@@ -497,7 +541,7 @@ def main():
             out["speedup_vs_cpu_all_cores"] = round(fps / allc["value"], 1) if allc["value"] else None
         # end to end through the plugin seam (host packets in, host pictures out; SURVEY 8d "End-to-end vs kernel (ii)"):
         # the C wrapper driven by tests/harness/plugin_harness.c in bench mode — never part of `value`
-        if world == 1 and not a.no_e2e:
+        if world == 1 and a.full and not a.no_e2e:
             try:
                 e2e = importlib.import_module("tools.e2e_bench")
                 r2 = e2e.run(w, h, packets=min(n, 64), repeat=17)  # the first lap is not timed (the session's allocations)
@@ -521,8 +565,9 @@ def main():
                 out["end_to_end"] = {"error": str(exc)[:200]}
         # what a plain streaming copy kernel sustains on this device (read + write), measured now: the second
         # yardstick of SURVEY.md section 8d next to the nominal peak (it overwrites half of the output: after the check)
-        half = (fsz * n // 2) & ~15
-        out["copy_ceiling_gbs"] = round(dev.copy_ceiling(r["d_out"], r["d_out"] + half, half), 1)
+        if a.full:
+            half = (fsz * n // 2) & ~15
+            out["copy_ceiling_gbs"] = round(dev.copy_ceiling(r["d_out"], r["d_out"] + half, half), 1)
 
     plan.close()
     dev.free(r["d_st"])
@@ -530,7 +575,7 @@ def main():
     barrier()  # ranks other than 0 wait here while rank 0 times the CPU legs
 
     # the same step at other launch sizes, fresh frames, never part of `value`
-    if world == 1 and rank == 0 and not a.no_sweep:
+    if world == 1 and rank == 0 and a.full and not a.no_sweep:
         sweep = {}
         for nb in (256, 1024, 4096):
             if nb >= n:
@@ -557,7 +602,7 @@ def main():
 
     # SURVEY.md section 8d's stress variant (noise +-64: 2.3 MB packets, nothing for the speculative index to lock on)
     # as a second, short, clearly labelled measurement; never part of `value`
-    if world == 1 and rank == 0 and not a.no_stress and a.amp != 64:
+    if world == 1 and rank == 0 and a.full and not a.no_stress and a.amp != 64:
         ns_frames = n  # the headline launch size
         # five warm-up launches: the plan's policy needs three to give the speculation up on this content (short lead lost,
         # long lead lost twice: k_spec_policy), after which the walkers return at once for 64 launches — the timed steps
