@@ -1,4 +1,5 @@
-// dv_common.h — what the host side and the gfx950 kernels of the DV25 decoder share.
+// dv_common.h — what the host side and the gfx950 kernels of the DV25 decoder share: the constant tables and the
+// two systems' frame and picture layouts.
 #pragma once
 #include <stdint.h>
 
@@ -24,6 +25,65 @@ struct Tables {
 
 constexpr int kFrameBytes = 120000, kW = 720, kH = 480, kCW = 180, kPicBytes = kW * kH * 3 / 2;
 constexpr int kSegments = 270;  // video segments per frame: 10 DIF sequences of 27
+
+#if defined(__HIP__) || defined(__HIPCC__)
+#define MIDV_HD __attribute__((host, device, always_inline)) inline
+#else
+#define MIDV_HD inline
+#endif
+
+// ---- the two 25 Mbit/s systems (include/mi_dv.h: MI_DV_SYS_*) ----
+// A DIF sequence is 150 blocks of 80 bytes in both; video block v (0..134) of a sequence is block 7 + v + v / 15, and
+// five consecutive video blocks are one video segment (27 per sequence).  What differs is the number of sequences, the
+// macroblock shuffle and the picture: place() maps macroblock m (0..4) of segment `slot` (0..26) of sequence `seq` to
+// its position, in the units the kernel's block placement uses.  The kernel and mi_dv_mb_place both call it.
+
+// 525/60 4:1:1: 10 sequences; 720 x 480, Cb / Cr 180 x 480.  Macroblocks are 32 x 8 pixels (four 8 x 8 luma blocks side
+// by side, one chroma block each) except in column 22, where they are 16 x 16 and their chroma blocks are split in
+// halves.  x in 32-pixel columns (0..22), y in 8-line rows (0..59); the shuffle the checker states too (dvo_mb_place).
+// The statement is also a macro: k_dv_decode<Sys525> expands it in place.  As a call it is inlined only after the callee
+// was simplified on its own, and the 525/60 kernel then compiles to other (no faster) code than it did before 625/50
+// existed; expanded, its code stays what it was, instruction for instruction.
+#define MIDV_PLACE_525(seq, slot, m, x32, y8)                                                 \
+  do {                                                                                        \
+    const uint32_t off_ = (m) == 0u ? 2u : (m) == 1u ? 6u : (m) == 2u ? 8u : (m) == 3u ? 0u : 4u;       \
+    const uint32_t start_ = (m) == 0u ? 9u : (m) == 1u ? 4u : (m) == 2u ? 13u : (m) == 3u ? 0u : 18u;   \
+    const uint32_t i_ = ((seq) + off_) % 10u;                                                 \
+    const uint32_t k_ = (slot) + ((m) == 1u || (m) == 2u ? 3u : 0u);                          \
+    const uint32_t k6_ = k_ / 6u, km_ = k_ - 6u * k6_;                                        \
+    const uint32_t serp_ = k6_ & 1u ? 5u - km_ : km_;                                         \
+    (x32) = start_ + k6_;                                                                     \
+    (y8) = (x32) > 21u ? 2u * serp_ + 6u * i_ : serp_ + 6u * i_;                              \
+  } while (0)
+struct Sys525 {
+  static constexpr int kId = 0;
+  static constexpr int kFrameBytes = 120000, kSeqs = 10, kSegments = kSeqs * 27, kPairs = kSegments / 2;
+  static constexpr int kW = 720, kH = 480, kCW = 180, kCH = 480, kPicBytes = kW * kH + 2 * kCW * kCH;
+  static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x32, uint32_t& y8) {
+    MIDV_PLACE_525(seq, slot, m, x32, y8);
+  }
+};
+
+// 625/50 IEC 4:2:0: 12 sequences; 720 x 576, Cb / Cr 360 x 288.  Every macroblock is 16 x 16 (Y0 Y1 / Y2 Y3, then one
+// 8 x 8 block of each chroma plane).  The picture is 45 x 36 macroblocks: 5 columns x 12 rows of super blocks of 9 x 3;
+// super block (row (seq + {2,6,8,0,4}[m]) mod 12, column {2,1,3,0,4}[m]), inside it column slot / 3 and row slot % 3,
+// upwards in odd columns.  x, y in 16-pixel units (0..44, 0..35).
+struct Sys625 {
+  static constexpr int kId = 1;
+  static constexpr int kFrameBytes = 144000, kSeqs = 12, kSegments = kSeqs * 27, kPairs = kSegments / 2;
+  static constexpr int kW = 720, kH = 576, kCW = 360, kCH = 288, kPicBytes = kW * kH + 2 * kCW * kCH;
+  static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x16, uint32_t& y16) {
+    const uint32_t off = m == 0u ? 2u : m == 1u ? 6u : m == 2u ? 8u : m == 3u ? 0u : 4u;
+    const uint32_t col = m == 0u ? 2u : m == 1u ? 1u : m == 2u ? 3u : m == 3u ? 0u : 4u;
+    const uint32_t row = (seq + off) % 12u;
+    const uint32_t c = slot / 3u, r = slot - 3u * c;
+    x16 = 9u * col + c;
+    y16 = 3u * row + (c & 1u ? 2u - r : r);
+  }
+};
+static_assert(Sys525::kFrameBytes == Sys525::kSeqs * 150 * 80 && Sys625::kFrameBytes == Sys625::kSeqs * 150 * 80, "DIF frames");
+static_assert(Sys525::kPicBytes == kPicBytes && Sys525::kFrameBytes == kFrameBytes && Sys525::kSegments == kSegments, "525/60");
+static_assert(Sys625::kPicBytes == 622080 && Sys625::kPairs * 2 == Sys625::kSegments, "625/50");
 
 // builds the tables (dv_tables.cpp); false if the code's lengths are not a complete prefix code
 bool build_tables(Tables* t);

@@ -1,7 +1,10 @@
-// dv_decode_kernels.h — gfx950 kernel of the DV25 525/60 video decoder (the arithmetic: DESIGN.md section 9; the
-// format: IEC 61834-2 / SMPTE 314M; nothing in the reference to follow — lib/dvframe.c:663-676 passes the DIF frame on).
+// dv_decode_kernels.h — gfx950 kernel of the DV25 video decoder, 525/60 4:1:1 and 625/50 4:2:0 (the arithmetic: DESIGN.md
+// section 9; the format: IEC 61834-2 / SMPTE 314M; nothing in the reference to follow — lib/dvframe.c:663-676 passes the
+// DIF frame on).
 //
-//   k_dv_decode    one wave per two video segments (2 x 5 compressed macroblocks = 60 blocks, one lane each):
+//   k_dv_decode<Sys>  one instantiation per system (dv_common.h: Sys525, Sys625), which differ only in the frame's
+//                  sequence count, the macroblock shuffle and where a block's pixels go.
+//                  One wave per two video segments (2 x 5 compressed macroblocks = 60 blocks, one lane each):
 //                  the three passes of the variable-length decode, reconstruction, both inverse transforms, placement.
 //                  A workgroup is kDvWaves such waves that share the constant tables in LDS and nothing else: the only
 //                  workgroup barrier is the one behind the table load; everything after it is ordered inside a wave.
@@ -28,8 +31,8 @@ constexpr int kLaneStride = MIDV_LANE_STRIDE;
 static_assert(kLaneStride >= 128 && kLaneStride % 16 == 0, "a lane's scratch: 64 int16, read 16 bytes at a time");
 constexpr int kDvWaves = MIDV_WAVES;  // waves per workgroup (2.9 KB of tables per workgroup instead of per wave)
 constexpr int kDvLive = 60;       // lanes of a wave that hold a block
-constexpr int kDvPairs = kSegments / 2;                             // waves a frame needs
-constexpr int kDvGridX = (kDvPairs + kDvWaves - 1) / kDvWaves;      // workgroups per frame
+template <class Sys>
+constexpr int kDvGridX = (Sys::kPairs + kDvWaves - 1) / kDvWaves;  // workgroups per frame (a wave per segment pair)
 constexpr int kMbufWords = 20;    // a macroblock's free space: at most 6 x 100 bits, + a dword to read past
 constexpr int kVbufWords = 86;    // a segment's: at most 2680 bits, + a dword to read past
 #ifndef MIDV_SKIP  // timing builds only (wrong pictures): 1 no pass 2 / 3, 2 no transforms and stores, 4 no pass 1
@@ -126,6 +129,7 @@ __device__ __forceinline__ void dv_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+template <class Sys>
 __global__ __launch_bounds__(64 * kDvWaves) void k_dv_decode(const uint8_t* __restrict__ frames, uint8_t* __restrict__ pics,
                                                    const Tables* __restrict__ T
 #ifdef MIDV_DEBUG
@@ -156,17 +160,17 @@ __global__ __launch_bounds__(64 * kDvWaves) void k_dv_decode(const uint8_t* __re
   for (int i = lane; i < 2 * kVbufWords; i += 64) (&s_vbuf[0][0])[i] = 0u;
   __syncthreads();  // the tables are there (the workgroup's only barrier: every wave reaches it, before anything can end one)
   const uint32_t pair = (uint32_t)blockIdx.x * (uint32_t)kDvWaves + wv;  // which two segments of the frame
-  if (pair >= (uint32_t)kDvPairs) return;
+  if (pair >= (uint32_t)Sys::kPairs) return;
 
   // ---- which block this lane has ----
   const bool live = lane < kDvLive;
   const uint32_t seg = (uint32_t)lane / 30u, b30 = (uint32_t)lane - 30u * seg, mbi = b30 / 6u, j = b30 - 6u * mbi;
   const uint32_t mb10 = (uint32_t)lane / 6u;  // macroblock of the wave, 0..9 (10: the idle lanes)
   uint32_t S = 2u * pair + seg;                // video segment of the frame
-  if (S >= (uint32_t)kSegments) S = kSegments - 1;  // (never: 270 is even)
+  if (S >= (uint32_t)Sys::kSegments) S = Sys::kSegments - 1;  // (never: 270 and 324 are even)
   const uint32_t seq = S / 27u, slot = S - 27u * seq;
   const uint32_t v = 5u * slot + mbi;
-  const uint8_t* mbp = frames + (size_t)blockIdx.y * kFrameBytes + (size_t)((seq * 150u + 7u + v + v / 15u) * 80u);
+  const uint8_t* mbp = frames + (size_t)blockIdx.y * Sys::kFrameBytes + (size_t)((seq * 150u + 7u + v + v / 15u) * 80u);
   const uint32_t ao = j < 4u ? 4u + 14u * j : 60u + 10u * (j - 4u);  // the block's area inside the compressed macroblock
   const uint32_t A = j < 4u ? 112u : 80u;                            // ... and its bits
   uint32_t W0, W1, W2, W3;  // the area's bits, MSB first, shifted left as they are consumed
@@ -353,7 +357,7 @@ __global__ __launch_bounds__(64 * kDvWaves) void k_dv_decode(const uint8_t* __re
 #ifdef MIDV_DEBUG
   if (dbg) {
     dv_wave_sync();
-    int16_t* o = dbg + (((size_t)blockIdx.y * kDvPairs + pair) * 64 + lane) * 72;
+    int16_t* o = dbg + (((size_t)blockIdx.y * Sys::kPairs + pair) * 64 + lane) * 72;
     for (int i = 0; i < 64; i++)  // natural order out of the scratch's (column pair, row) layout
       o[i] = ((const int16_t*)my)[2 * (8 * ((i & 7) >> 1) + (i >> 3)) + (i & 1)];
     o[64] = (int16_t)pos; o[65] = (int16_t)p; o[66] = (int16_t)fin; o[67] = (int16_t)npart; o[68] = (int16_t)mode; o[69] = (int16_t)cls;
@@ -374,30 +378,38 @@ __global__ __launch_bounds__(64 * kDvWaves) void k_dv_decode(const uint8_t* __re
   }
   const bool pk = __all(!live || mirtj::pk_range_full(q, K));
   if (!live || (MIDV_SKIP & 2)) return;
-  // where the block goes (525/60 4:1:1 macroblock shuffling and placement)
-  uint32_t x32, y8;
-  {
-    const uint32_t off = mbi == 0u ? 2u : mbi == 1u ? 6u : mbi == 2u ? 8u : mbi == 3u ? 0u : 4u;
-    const uint32_t start = mbi == 0u ? 9u : mbi == 1u ? 4u : mbi == 2u ? 13u : mbi == 3u ? 0u : 18u;
-    const uint32_t i = (seq + off) % 10u;
-    const uint32_t k = slot + (mbi == 1u || mbi == 2u ? 3u : 0u);
-    const uint32_t k6 = k / 6u, km = k - 6u * k6;
-    const uint32_t serp = k6 & 1u ? 5u - km : km;
-    x32 = start + k6;
-    y8 = x32 > 21u ? 2u * serp + 6u * i : serp + 6u * i;
-  }
-  uint8_t* pic = pics + (size_t)blockIdx.y * kPicBytes;
+  // where the block goes (the system's macroblock shuffling and placement)
+  uint32_t mx, my8;
+  if constexpr (Sys::kId == Sys525::kId)
+    MIDV_PLACE_525(seq, slot, mbi, mx, my8);  // (Sys525::place, expanded: dv_common.h)
+  else
+    Sys::place(seq, slot, mbi, mx, my8);
+  uint8_t* pic = pics + (size_t)blockIdx.y * Sys::kPicBytes;
   typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
-  const bool edge = x32 == 22u;
   uint32_t stride, org;
-  if (j < 4u) {
-    stride = kW;
-    org = edge ? (8u * y8 + 8u * (j >> 1)) * kW + 32u * x32 + 8u * (j & 1u) : 8u * y8 * kW + 32u * x32 + 8u * j;
-  } else {
-    stride = kCW;
-    org = kW * kH + (j == 4u ? kCW * kH : 0u) + 8u * y8 * kCW + 8u * x32;  // block 4 is Cr (third plane), block 5 Cb
+  bool halves = false;
+  if constexpr (Sys::kId == Sys525::kId) {  // mx: 32-pixel column, my8: 8-line row
+    const uint32_t x32 = mx, y8 = my8;
+    const bool edge = x32 == 22u;
+    if (j < 4u) {
+      stride = kW;
+      org = edge ? (8u * y8 + 8u * (j >> 1)) * kW + 32u * x32 + 8u * (j & 1u) : 8u * y8 * kW + 32u * x32 + 8u * j;
+    } else {
+      stride = kCW;
+      org = kW * kH + (j == 4u ? kCW * kH : 0u) + 8u * y8 * kCW + 8u * x32;  // block 4 is Cr (third plane), block 5 Cb
+    }
+    halves = j >= 4u && edge;  // the right-edge chroma block: left half here, right half eight lines below
+  } else {  // 625/50: 16 x 16 macroblocks everywhere (mx, my8: their column and row), whole 8-byte rows
+    constexpr uint32_t W = Sys::kW, H = Sys::kH, CW = Sys::kCW, CH = Sys::kCH;
+    const uint32_t x16 = mx, y16 = my8;
+    if (j < 4u) {
+      stride = W;
+      org = (16u * y16 + 8u * (j >> 1)) * W + 16u * x16 + 8u * (j & 1u);
+    } else {
+      stride = CW;
+      org = W * H + (j == 4u ? CW * CH : 0u) + 8u * y16 * CW + 8u * x16;  // block 4 is Cr (third plane), block 5 Cb
+    }
   }
-  const bool halves = j >= 4u && edge;  // the right-edge chroma block: left half here, right half eight lines below
   auto put = [&](int r, uint32_t lo, uint32_t hi) {
     if (halves) {
       *(uint32_t*)(pic + org + (uint32_t)r * stride) = lo;

@@ -1,4 +1,4 @@
-// mi_dv.hip — C ABI (include/mi_dv.h) of the MI355X DV25 525/60 decoder.  No CPU path: without a gfx950 device
+// mi_dv.hip — C ABI (include/mi_dv.h) of the MI355X DV25 decoder (525/60 4:1:1, 625/50 4:2:0).  No CPU path: without a gfx950 device
 // every call fails with a message.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -17,6 +17,10 @@
 using namespace midv;
 
 static_assert(MI_DV_FRAME_BYTES == kFrameBytes && MI_DV_PICTURE_BYTES == kPicBytes, "header and kernels agree");
+static_assert(MI_DV_625_FRAME_BYTES == Sys625::kFrameBytes && MI_DV_625_PICTURE_BYTES == Sys625::kPicBytes &&
+                  MI_DV_625_HEIGHT == Sys625::kH && MI_DV_625_CHROMA_WIDTH == Sys625::kCW &&
+                  MI_DV_625_CHROMA_HEIGHT == Sys625::kCH && MI_DV_SYS_525_60 == Sys525::kId && MI_DV_SYS_625_50 == Sys625::kId,
+              "header and kernels agree (625/50)");
 
 namespace {
 std::mutex g_mu;
@@ -29,10 +33,11 @@ struct mi_dv_ctx {
   Tables* d_tab = nullptr;
   // one pair of events around every launch since the last mi_dv_kernel_times (recycled there)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_used, ev_free;
-  // the one-frame path's buffers
+  // the one-frame path's buffers (525/60 sizes, or 625/50 ones once a 625/50 frame came: big enough for both)
   uint8_t* d_frame = nullptr;
   uint8_t* d_pic = nullptr;
   uint8_t* h_pic = nullptr;  // pinned
+  bool one_625 = false;
   std::string err;
 };
 
@@ -164,11 +169,16 @@ int mi_dv_sync(mi_dv_ctx* c) {
 static void* g_dbg = nullptr;
 extern "C" void mi_dv_debug_buffer(void* d) { g_dbg = d; }
 #endif
-int mi_dv_decode_batch(mi_dv_ctx* c, const void* d_frames, int n, void* d_pics) {
-  if (!c || !d_frames || !d_pics || n <= 0) return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_batch: bad argument");
-  if (n > 65535) return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_batch: %d frames; at most 65535 per call (split the batch)", n);
+}  // extern "C"
+
+namespace {
+// the launch of either system's kernel, with its events (`who`: the entry point the messages name)
+template <class Sys>
+int launch(mi_dv_ctx* c, const char* who, const void* d_frames, int n, void* d_pics) {
+  if (!c || !d_frames || !d_pics || n <= 0) return fail(c, MI_DV_ERR_ARG, "%s: bad argument", who);
+  if (n > 65535) return fail(c, MI_DV_ERR_ARG, "%s: %d frames; at most 65535 per call (split the batch)", who, n);
   if (((uintptr_t)d_frames & 3u) || ((uintptr_t)d_pics & 7u))
-    return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_batch: d_frames must be 4-byte and d_pics 8-byte aligned");
+    return fail(c, MI_DV_ERR_ARG, "%s: d_frames must be 4-byte and d_pics 8-byte aligned", who);
   DVCHK(c, hipSetDevice(c->device));
   std::pair<hipEvent_t, hipEvent_t> ev;
   if (!c->ev_free.empty()) {
@@ -184,8 +194,8 @@ int mi_dv_decode_batch(mi_dv_ctx* c, const void* d_frames, int n, void* d_pics) 
     c->ev_used.erase(c->ev_used.begin());
   }
   DVCHK(c, hipEventRecord(ev.first, c->stream));
-  hipLaunchKernelGGL(k_dv_decode, dim3(kDvGridX, (unsigned)n), dim3(64 * kDvWaves), 0, c->stream, (const uint8_t*)d_frames,
-                     (uint8_t*)d_pics, c->d_tab
+  hipLaunchKernelGGL(k_dv_decode<Sys>, dim3(kDvGridX<Sys>, (unsigned)n), dim3(64 * kDvWaves), 0, c->stream,
+                     (const uint8_t*)d_frames, (uint8_t*)d_pics, c->d_tab
 #ifdef MIDV_DEBUG
                      , (int16_t*)g_dbg
 #endif
@@ -193,6 +203,19 @@ int mi_dv_decode_batch(mi_dv_ctx* c, const void* d_frames, int n, void* d_pics) 
   DVCHK(c, hipGetLastError());
   DVCHK(c, hipEventRecord(ev.second, c->stream));
   return MI_DV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mi_dv_decode_batch(mi_dv_ctx* c, const void* d_frames, int n, void* d_pics) {
+  return launch<Sys525>(c, "mi_dv_decode_batch", d_frames, n, d_pics);
+}
+
+int mi_dv_decode_batch_sys(mi_dv_ctx* c, int system, const void* d_frames, int n, void* d_pics) {
+  if (system == MI_DV_SYS_525_60) return launch<Sys525>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
+  if (system == MI_DV_SYS_625_50) return launch<Sys625>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
+  return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_batch_sys: unknown system %d", system);
 }
 
 int mi_dv_kernel_times(mi_dv_ctx* c, float* total_ms, int* launches) {
@@ -244,6 +267,65 @@ int mi_dv_decode_frame(mi_dv_ctx* c, const uint8_t* frame, size_t len, uint8_t* 
     for (int y = 0; y < kH; y++) memcpy(planes[pl] + (size_t)y * strides[pl], src + (size_t)y * w, (size_t)w);
     src += (size_t)w * kH;
   }
+  return MI_DV_OK;
+}
+
+int mi_dv_system_of(const uint8_t* frame, size_t len) {
+  // dv_frame_profile (lib/dvframe.c:298-316): DSF = byte 3 bit 7, APT = byte 5 & 7, stype = byte 80*5+48+3 & 0x1f
+  if (!frame || len < 80 * 6) return -1;
+  const int dsf = frame[3] >> 7, apt = frame[5] & 7, stype = frame[80 * 5 + 48 + 3] & 0x1f;
+  if (stype != 0) return -1;  // DVCPRO50 and the HD profiles
+  if (dsf == 0) return len >= (size_t)Sys525::kFrameBytes ? MI_DV_SYS_525_60 : -1;
+  if (apt != 0) return -1;  // DVCPRO 625/50 4:1:1 (lib/dvframe.c:303)
+  return len >= (size_t)Sys625::kFrameBytes ? MI_DV_SYS_625_50 : -1;
+}
+
+int mi_dv_decode_frame_sys(mi_dv_ctx* c, int system, const uint8_t* frame, size_t len, uint8_t* const planes[3],
+                           const int strides[3]) {
+  if (system == MI_DV_SYS_525_60) return mi_dv_decode_frame(c, frame, len, planes, strides);
+  if (system != MI_DV_SYS_625_50) return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame_sys: unknown system %d", system);
+  using S = Sys625;
+  if (!c || !frame || !planes || !strides || !planes[0] || !planes[1] || !planes[2])
+    return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame_sys: NULL argument");
+  if (len < (size_t)S::kFrameBytes) return fail(c, MI_DV_ERR_FORMAT, "DIF frame of %zu bytes: 625/50 frames have %d", len, S::kFrameBytes);
+  if (mi_dv_system_of(frame, len) != MI_DV_SYS_625_50)
+    return fail(c, MI_DV_ERR_FORMAT, "not a 625/50 25 Mbit/s 4:2:0 DV frame (DSF %d, APT %d, stype 0x%02x)", frame[3] >> 7,
+                frame[5] & 7, frame[80 * 5 + 48 + 3] & 0x1f);
+  if (strides[0] < S::kW || strides[1] < S::kCW || strides[2] < S::kCW) return fail(c, MI_DV_ERR_ARG, "strides below the picture's width");
+  DVCHK(c, hipSetDevice(c->device));
+  if (!c->one_625) {  // once per instance: replaces the 525/60-sized buffers (the stream is idle between calls)
+    if (c->d_frame) DVCHK(c, hipFree(c->d_frame));
+    if (c->d_pic) DVCHK(c, hipFree(c->d_pic));
+    if (c->h_pic) DVCHK(c, hipHostFree(c->h_pic));
+    c->d_frame = c->d_pic = c->h_pic = nullptr;
+    DVCHK(c, hipMalloc((void**)&c->d_frame, S::kFrameBytes));
+    DVCHK(c, hipMalloc((void**)&c->d_pic, S::kPicBytes));
+    DVCHK(c, hipHostMalloc((void**)&c->h_pic, S::kPicBytes, hipHostMallocDefault));
+    c->one_625 = true;
+  }
+  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, S::kFrameBytes, hipMemcpyHostToDevice, c->stream));
+  const int rc = launch<S>(c, "mi_dv_decode_frame_sys", c->d_frame, 1, c->d_pic);
+  if (rc != MI_DV_OK) return rc;
+  DVCHK(c, hipMemcpyAsync(c->h_pic, c->d_pic, S::kPicBytes, hipMemcpyDeviceToHost, c->stream));
+  DVCHK(c, hipStreamSynchronize(c->stream));
+  const uint8_t* src = c->h_pic;
+  for (int pl = 0; pl < 3; pl++) {
+    const int w = pl ? S::kCW : S::kW, h = pl ? S::kCH : S::kH;
+    for (int y = 0; y < h; y++) memcpy(planes[pl] + (size_t)y * strides[pl], src + (size_t)y * w, (size_t)w);
+    src += (size_t)w * h;
+  }
+  return MI_DV_OK;
+}
+
+int mi_dv_mb_place(int system, int seq, int slot, int m, int* x, int* y) {
+  const int seqs = system == MI_DV_SYS_525_60 ? Sys525::kSeqs : system == MI_DV_SYS_625_50 ? Sys625::kSeqs : 0;
+  if (!x || !y || seq < 0 || seq >= seqs || slot < 0 || slot >= 27 || m < 0 || m >= 5)
+    return fail(nullptr, MI_DV_ERR_ARG, "mi_dv_mb_place: system %d, sequence %d, segment %d, macroblock %d out of range", system, seq, slot, m);
+  uint32_t ux, uy;
+  if (system == MI_DV_SYS_525_60) Sys525::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
+  else Sys625::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
+  *x = (int)ux;
+  *y = (int)uy;
   return MI_DV_OK;
 }
 

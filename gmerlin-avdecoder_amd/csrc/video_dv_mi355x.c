@@ -1,12 +1,16 @@
 /*
- * video_dv_mi355x.c — a bgav_video_decoder_t for DV25 525/60 (NTSC) video on an MI355X.
+ * video_dv_mi355x.c — a bgav_video_decoder_t for DV25 video on an MI355X: 525/60 (NTSC, 4:1:1) and 625/50 (PAL) in
+ * the IEC 4:2:0 profile.
  *
  * In gmerlin-avdecoder DV pixels are libavcodec's: lib/dvframe.c:663-676 hands each 120,000-byte DIF frame on as a
  * video packet, and the "FFmpeg DV decoder" entry of lib/video_ffmpeg.c:1572-1575 decodes it for the fourccs of
  * lib/video.c:122-145 (bgav_dv_fourccs).  This file registers a decoder for the same fourccs that is asked FIRST
  * (first match wins, lib/codecs.c:246-279): its .probe accepts a stream only when a gfx950 device is usable and the
- * stream is 720 x 480, so every other DV flavour (625/50, DVCPRO50, DVCPRO HD) and every host without the device still
- * go to the FFmpeg decoder.  The pixels come from include/mi_dv.h.
+ * stream is 720 x 480, or 720 x 576 with the pixel format GAVL_YUV_420_P.  The demultiplexer sets that pixel format
+ * from the DIF profile (lib/dvframe.c:490-500; lib/parse_dv.c:51 for DV in other containers), so a 625/50 stream is
+ * ours only in the IEC 4:2:0 profile.  Every other DV flavour (DVCPRO 625/50 4:1:1, a 720 x 576 stream whose pixel
+ * format is not known, DVCPRO50, DVCPRO HD) and every host without the device still go to the FFmpeg decoder.  The
+ * pixels come from include/mi_dv.h: mi_dv_decode_frame_sys with the system the stream was opened with.
  *
  * Integration: add this file to lib/Makefile.am, declare
  * bgav_init_video_decoders_dv_mi355x() in include/codecs.h and call it in bgav_codecs_init (lib/codecs.c:160-200) BEFORE
@@ -29,6 +33,7 @@
 
 typedef struct {
   mi_dv_ctx *ctx;
+  int system; /* MI_DV_SYS_525_60 or MI_DV_SYS_625_50, from the stream's format */
 } dv_hip_priv_t;
 
 /* the fourccs of lib/video.c:122-145; inside the tree the library's own array is used */
@@ -43,19 +48,27 @@ static const uint32_t dv_fourccs[] = {
 #define DV_FOURCCS bgav_dv_fourccs /* include/avdec_private.h:1435 */
 #endif
 
-static int is_525_60(const gavl_video_format_t *fmt) { return fmt && fmt->image_width == MI_DV_WIDTH && fmt->image_height == MI_DV_HEIGHT; }
+/* the system of a stream by its format: 720 x 480 is 525/60; 720 x 576 is 625/50 only in the 4:2:0 profile; -1 else */
+static int dv_system(const gavl_video_format_t *fmt) {
+  if (!fmt || fmt->image_width != MI_DV_WIDTH) return -1;
+  if (fmt->image_height == MI_DV_HEIGHT) return MI_DV_SYS_525_60;
+  if (fmt->image_height == MI_DV_625_HEIGHT && fmt->pixelformat == GAVL_YUV_420_P) return MI_DV_SYS_625_50;
+  return -1;
+}
 
 /* .probe (include/avdec_private.h:95): only what this decoder can do, so that the FFmpeg decoder registered behind it
  * gets everything else */
 static int probe_dv_hip(const gavl_dictionary_t *stream) {
   if (mi_dv_device_count() <= 0) return 0;
-  return is_525_60(gavl_stream_get_video_format(stream));
+  return dv_system(gavl_stream_get_video_format(stream)) >= 0;
 }
 
 static int init_dv_hip(bgav_stream_t *s) {
   dv_hip_priv_t *priv;
-  if (!is_525_60(s->data.video.format)) { /* (a caller that skipped .probe) */
-    gavl_log(GAVL_LOG_ERROR, LOG_DOMAIN, "Only 525/60 25 Mbit/s DV (720x480) is decoded on the MI355X");
+  const int system = dv_system(s->data.video.format);
+  if (system < 0) { /* (a caller that skipped .probe) */
+    gavl_log(GAVL_LOG_ERROR, LOG_DOMAIN,
+             "Only 525/60 (720x480) and 625/50 4:2:0 (720x576) 25 Mbit/s DV are decoded on the MI355X");
     return 0;
   }
   priv = calloc(1, sizeof(*priv));
@@ -66,10 +79,15 @@ static int init_dv_hip(bgav_stream_t *s) {
     free(priv);
     return 0;
   }
+  priv->system = system;
   s->decoder_priv = priv;
   s->data.video.format->frame_width = MI_DV_WIDTH;
-  s->data.video.format->frame_height = MI_DV_HEIGHT;
-  s->data.video.format->pixelformat = GAVL_YUV_411_P; /* lib/dvframe.c:119: the 525/60 profile's pix_fmt */
+  if (system == MI_DV_SYS_525_60) {
+    s->data.video.format->frame_height = MI_DV_HEIGHT;
+    s->data.video.format->pixelformat = GAVL_YUV_411_P; /* lib/dvframe.c:119: the 525/60 profile's pix_fmt */
+  } else {
+    s->data.video.format->frame_height = MI_DV_625_HEIGHT; /* the pixel format stays GAVL_YUV_420_P (lib/dvframe.c:129-148) */
+  }
   gavl_dictionary_set_string(s->m, GAVL_META_FORMAT, "DV");
   return 1;
 }
@@ -83,7 +101,8 @@ static gavl_source_status_t decode_dv_hip(bgav_stream_t *s, gavl_video_frame_t *
     bgav_stream_done_packet_read(s, p);
     return GAVL_SOURCE_OK;
   }
-  if (mi_dv_decode_frame(priv->ctx, p->buf.buf, (size_t)p->buf.len, (uint8_t *const *)f->planes, f->strides) != MI_DV_OK) {
+  if (mi_dv_decode_frame_sys(priv->ctx, priv->system, p->buf.buf, (size_t)p->buf.len, (uint8_t *const *)f->planes,
+                             f->strides) != MI_DV_OK) {
     gavl_log(GAVL_LOG_ERROR, LOG_DOMAIN, "Decoding failed: %s", mi_dv_last_error(priv->ctx));
     bgav_stream_done_packet_read(s, p);
     return GAVL_SOURCE_EOF; /* never abort: errors are EOF + a log line, as everywhere in the library */

@@ -1,4 +1,4 @@
-"""ctypes view of include/mi_dv.h (libmi_dv.so, the DV25 525/60 decoder).  No CPU path: without the library or a
+"""ctypes view of include/mi_dv.h (libmi_dv.so, the DV25 decoder: 525/60 4:1:1 and 625/50 4:2:0).  No CPU path: without the library or a
 gfx950 device construction raises MiDvError with the library's own message."""
 import ctypes as C
 import os
@@ -7,9 +7,14 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FRAME_BYTES, PICTURE_BYTES, W, H, CW = 120000, 720 * 480 * 3 // 2, 720, 480, 180
+SYS_525_60, SYS_625_50 = 0, 1
+FRAME_BYTES_625, PICTURE_BYTES_625, H_625, CW_625, CH_625 = 144000, 720 * 576 + 2 * 360 * 288, 576, 360, 288
+# per system: frame bytes, picture bytes, (width, height) of the planes Y, Cb, Cr
+GEOMETRY = {SYS_525_60: (FRAME_BYTES, PICTURE_BYTES, ((W, H), (CW, H), (CW, H))),
+            SYS_625_50: (FRAME_BYTES_625, PICTURE_BYTES_625, ((W, H_625), (CW_625, CH_625), (CW_625, CH_625)))}
 EXPORTS = ["mi_dv_device_count", "mi_dv_create", "mi_dv_destroy", "mi_dv_last_error", "mi_dv_dev_alloc", "mi_dv_dev_free",
            "mi_dv_h2d", "mi_dv_d2h", "mi_dv_sync", "mi_dv_decode_batch", "mi_dv_kernel_times", "mi_dv_decode_frame",
-           "mi_dv_copy_tables"]
+           "mi_dv_copy_tables", "mi_dv_system_of", "mi_dv_decode_batch_sys", "mi_dv_decode_frame_sys", "mi_dv_mb_place"]
 _LIB = None
 u8p = C.POINTER(C.c_uint8)
 
@@ -50,6 +55,10 @@ def load():
     L.mi_dv_decode_frame.argtypes = [vp, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int)]
     L.mi_dv_copy_tables.argtypes = [vp, C.c_size_t]
     L.mi_dv_copy_tables.restype = C.c_size_t
+    L.mi_dv_system_of.argtypes = [u8p, C.c_size_t]
+    L.mi_dv_decode_batch_sys.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    L.mi_dv_decode_frame_sys.argtypes = [vp, C.c_int, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int)]
+    L.mi_dv_mb_place.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2
     _LIB = L
     return L
 
@@ -61,6 +70,29 @@ def tables():
     a = np.zeros(n // 4, np.uint32)
     L.mi_dv_copy_tables(a.ctypes.data, n)
     return {"lut9": a[:512], "lut2": a[512:576], "tab": a[576:704].reshape(2, 64), "shift4": a[704:728]}
+
+
+def geometry(system):
+    """(frame bytes, picture bytes, ((w, h) of Y, Cb, Cr)) of a system"""
+    if system not in GEOMETRY:
+        raise MiDvError(f"unknown DV system {system}")
+    return GEOMETRY[system]
+
+
+def system_of(frame):
+    """the system a DIF frame announces (SYS_525_60 / SYS_625_50), -1 for other profiles and short frames (host-side)"""
+    frame = np.ascontiguousarray(frame, np.uint8)
+    return load().mi_dv_system_of(frame.ctypes.data_as(u8p), frame.nbytes)
+
+
+def mb_place(system, seq, slot, m):
+    """the kernels' placement of macroblock m of segment `slot` of sequence `seq`: (x, y) — 525/60 in 32-pixel columns and
+    8-line rows, 625/50 in 16 x 16 macroblocks (host-side)"""
+    x, y = C.c_int(), C.c_int()
+    L = load()
+    if L.mi_dv_mb_place(system, seq, slot, m, C.byref(x), C.byref(y)) != 0:
+        raise MiDvError(L.mi_dv_last_error(None).decode())
+    return x.value, y.value
 
 
 class MiDv:
@@ -98,32 +130,47 @@ class MiDv:
     def decode_batch(self, d_frames, n, d_pics):
         self._chk(self.L.mi_dv_decode_batch(self.c, d_frames, n, d_pics))
 
+    def decode_batch_sys(self, system, d_frames, n, d_pics):
+        self._chk(self.L.mi_dv_decode_batch_sys(self.c, system, d_frames, n, d_pics))
+
     def kernel_times(self):
         """(total milliseconds, launches) of k_dv_decode since the last call"""
         ms, n = C.c_float(), C.c_int()
         self._chk(self.L.mi_dv_kernel_times(self.c, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
-    def decode_frames(self, frames):
-        """host frames (n x 120000 uint8) -> host pictures (n x 518400), through the batch path"""
-        frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, FRAME_BYTES)
+    def decode_frames(self, frames, system=SYS_525_60):
+        """host frames (n x the system's frame bytes, uint8) -> host pictures (n x its picture bytes), through the batch
+        path (525/60: 120000 -> 518400; 625/50: 144000 -> 622080)"""
+        fb, pb, _ = geometry(system)
+        frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, fb)
         n = frames.shape[0]
-        df, dp = self.alloc(n * FRAME_BYTES), self.alloc(n * PICTURE_BYTES)
+        df, dp = self.alloc(n * fb), self.alloc(n * pb)
         try:
             self.h2d(df, frames)
-            self.decode_batch(df, n, dp)
+            if system == SYS_525_60:
+                self.decode_batch(df, n, dp)
+            else:
+                self.decode_batch_sys(system, df, n, dp)
             self.sync()
-            return self.d2h(dp, n * PICTURE_BYTES).reshape(n, PICTURE_BYTES)
+            return self.d2h(dp, n * pb).reshape(n, pb)
         finally:
             self.free(df)
             self.free(dp)
 
-    def decode_frame(self, frame, strides=(W, CW, CW)):
+    def decode_frame(self, frame, strides=None, system=SYS_525_60):
+        """one host frame into three planes of the given strides (default: the system's plane widths)"""
+        _, _, planes_wh = geometry(system)
+        if strides is None:
+            strides = tuple(w for w, _ in planes_wh)
         frame = np.ascontiguousarray(frame, np.uint8)
-        planes = [np.zeros(strides[i] * H, np.uint8) for i in range(3)]
+        planes = [np.zeros(strides[i] * planes_wh[i][1], np.uint8) for i in range(3)]
         pp = (u8p * 3)(*[p.ctypes.data_as(u8p) for p in planes])
         st = (C.c_int * 3)(*strides)
-        self._chk(self.L.mi_dv_decode_frame(self.c, frame.ctypes.data_as(u8p), frame.nbytes, pp, st))
+        if system == SYS_525_60:
+            self._chk(self.L.mi_dv_decode_frame(self.c, frame.ctypes.data_as(u8p), frame.nbytes, pp, st))
+        else:
+            self._chk(self.L.mi_dv_decode_frame_sys(self.c, system, frame.ctypes.data_as(u8p), frame.nbytes, pp, st))
         return planes
 
     def close(self):

@@ -1,5 +1,6 @@
 /*
- * mi_dv.h — C ABI of the MI355X (gfx950) DV25 525/60 video decoder: 120,000-byte DIF frames in, 720 x 480 4:1:1
+ * mi_dv.h — C ABI of the MI355X (gfx950) DV25 video decoder.  Two systems: 525/60 (NTSC), 120,000-byte DIF frames in,
+ * 720 x 480 4:1:1 pictures out; and 625/50 (PAL) in the IEC 4:2:0 profile, 144,000-byte DIF frames in, 720 x 576 4:2:0
  * pictures out.  Plain C types only; libmi_dv.so.
  *
  * Where it sits in gmerlin-avdecoder.  lib/dvframe.c:663-676 (bgav_dv_dec_get_video_packet) hands every DIF frame on
@@ -7,12 +8,16 @@
  * lib/video_ffmpeg.c:556,628 (table entry :1572-1575; the fourccs 'dvc ', 'dvcp', 'dvsd', ... of lib/video.c:122-145).
  * This library replaces that step for the 525/60 25 Mbit/s profile: a decoder
  * registered for those fourccs in front of the FFmpeg one calls mi_dv_decode_frame with
- * gavl_packet_t::buf and the planes / strides of the gavl_video_frame_t (GAVL_YUV_411_P: Y, Cb, Cr).
+ * gavl_packet_t::buf and the planes / strides of the gavl_video_frame_t (GAVL_YUV_411_P: Y, Cb, Cr).  For the 625/50
+ * 4:2:0 profile (lib/dvframe.c:129-148, GAVL_YUV_420_P) it calls mi_dv_decode_frame_sys with MI_DV_SYS_625_50.  The
+ * other profiles of lib/dvframe.c:106-296 (DVCPRO 625/50 4:1:1, DVCPRO50, DVCPRO HD) are not decoded here.
  *
  * PARITY UNPINNED: the reference holds no DV pixel decoder to compare with and none is reachable from the build
  * container.  The arithmetic is stated in oracle/dv_oracle.c (written from the published format, from memory); the
  * GPU path reproduces THAT bit for bit.  Pictures of a real DV stream will look right only as far as that statement
- * matches the standard's tables.
+ * matches the standard's tables.  The 625/50 layout (the number of DIF sequences, the macroblock shuffle, the 4:2:0
+ * block placement: DESIGN.md section 9) is written from the published format too and is just as unpinned; its checker,
+ * tests/dv625.py, moves whole video segments between 625/50 and 525/60 frames around the unchanged oracle.
  */
 #ifndef MI_DV_H
 #define MI_DV_H
@@ -25,6 +30,10 @@ extern "C" {
 enum { MI_DV_OK = 0, MI_DV_ERR_ARG = -1, MI_DV_ERR_HIP = -2, MI_DV_ERR_NOMEM = -3, MI_DV_ERR_FORMAT = -4 };
 enum { MI_DV_FRAME_BYTES = 120000, MI_DV_WIDTH = 720, MI_DV_HEIGHT = 480, MI_DV_CHROMA_WIDTH = 180,
        MI_DV_PICTURE_BYTES = 720 * 480 * 3 / 2 };
+/* the systems (the DSF bit of the DIF header), and the 625/50 geometry: Y 720 x 576, Cb 360 x 288, Cr 360 x 288 */
+enum { MI_DV_SYS_525_60 = 0, MI_DV_SYS_625_50 = 1 };
+enum { MI_DV_625_FRAME_BYTES = 144000, MI_DV_625_HEIGHT = 576, MI_DV_625_CHROMA_WIDTH = 360, MI_DV_625_CHROMA_HEIGHT = 288,
+       MI_DV_625_PICTURE_BYTES = 720 * 576 + 2 * 360 * 288 };
 
 typedef struct mi_dv_ctx mi_dv_ctx;
 
@@ -59,6 +68,26 @@ int mi_dv_decode_frame(mi_dv_ctx *c, const uint8_t *frame, size_t len, uint8_t *
  * shifts).  Host only — no device needed: the non-GPU tests compare them with what oracle/dv_oracle.c makes of the same
  * format data.  Returns the size in bytes; copies when `out` has room. */
 size_t mi_dv_copy_tables(void *out, size_t cap);
+
+/* ---- both systems ---- */
+
+/* The system a DIF frame of `len` bytes belongs to, from its header (lib/dvframe.c:298-316): MI_DV_SYS_525_60 for DSF 0
+ * with VAUX stype 0, MI_DV_SYS_625_50 for DSF 1 with stype 0 and APT 0; -1 for anything else (DVCPRO 625/50 4:1:1, which
+ * is DSF 1 with APT != 0; DVCPRO50; the HD profiles) and for a frame shorter than its system's.  Host only. */
+int mi_dv_system_of(const uint8_t *frame, size_t len);
+/* mi_dv_decode_batch for either system: frames of the system's size in, pictures of the system's size out
+ * (MI_DV_625_FRAME_BYTES / MI_DV_625_PICTURE_BYTES for 625/50: Y 720 x 576, Cb 360 x 288, Cr 360 x 288, tightly
+ * packed).  The same rules on alignment, batch size and kernel times; for MI_DV_SYS_525_60 the same output byte for
+ * byte.  MI_DV_ERR_ARG for an unknown system. */
+int mi_dv_decode_batch_sys(mi_dv_ctx *c, int system, const void *d_frames, int n, void *d_pics);
+/* mi_dv_decode_frame for either system (for MI_DV_SYS_525_60 it is that function).  MI_DV_ERR_FORMAT for a frame that
+ * does not announce `system` or is shorter than its frames; MI_DV_ERR_ARG for an unknown system. */
+int mi_dv_decode_frame_sys(mi_dv_ctx *c, int system, const uint8_t *frame, size_t len, uint8_t *const planes[3],
+                           const int strides[3]);
+/* The kernels' own macroblock placement: macroblock m (0..4) of video segment `slot` (0..26) of DIF sequence `seq`.
+ * 525/60: x in 32-pixel columns, y in 8-line rows (a column-22 macroblock is 16 x 16 pixels), as in the oracle;
+ * 625/50: x, y in 16 x 16 macroblocks (0..44, 0..35).  Host only; MI_DV_ERR_ARG for arguments out of range. */
+int mi_dv_mb_place(int system, int seq, int slot, int m, int *x, int *y);
 
 #ifdef __cplusplus
 }
