@@ -32,7 +32,8 @@ EXPORTS = ["mi_rtj_device_count", "mi_rtj_create", "mi_rtj_destroy", "mi_rtj_las
            "mi_rtj_copy_ceiling", "mi_rtj_plan_spec_stats", "mi_rtj_plan_spec_lead", "mi_rtj_plan_decode_form", "mi_rtj_plan_overlapped",
            "mi_rtj_plan_step_times", "mi_rtj_pipe_create", "mi_rtj_pipe_destroy", "mi_rtj_pipe_room",
            "mi_rtj_pipe_pending", "mi_rtj_pipe_submit", "mi_rtj_pipe_next", "mi_rtj_pipe_peek_tag", "mi_rtj_pipe_flush",
-           "mi_rtj_pipe_profile", "mi_rtj_pipe_times"]
+           "mi_rtj_pipe_profile", "mi_rtj_pipe_times", "mi_rtj_plan_set_runs", "mi_rtj_plan_run_times",
+           "mi_rtj_plan_run_stats"]
 
 
 KERNELS = ("k_index_summarize", "k_index_resolve", "k_index_emit", "k_decode", "k_spec_walk", "k_spec_verify")
@@ -75,6 +76,9 @@ def load():
     L.mi_rtj_plan_decode_form.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
     L.mi_rtj_plan_overlapped.argtypes = [vp]
     L.mi_rtj_plan_step_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
+    L.mi_rtj_plan_set_runs.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.mi_rtj_plan_run_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    L.mi_rtj_plan_run_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.mi_rtj_pipe_create.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.mi_rtj_pipe_create.restype = vp
     L.mi_rtj_pipe_destroy.argtypes = [vp]
@@ -179,6 +183,25 @@ class Plan:
         n = C.c_int()
         self.owner._chk(self.owner.L.mi_rtj_plan_times(self.h, ms, C.byref(n)))
         return dict(zip(KERNELS, [float(x) for x in ms])), n.value
+
+    def set_runs(self, lengths):
+        """Cut the plan into runs of consecutive pictures of one stream (include/mi_rtjpeg.h, "runs"); [] or None:
+        independent pictures again.  Raises MiRtjError (and leaves the plan as it was) on a refused cut."""
+        lengths = [int(x) for x in (lengths or [])]
+        arr = (C.c_int * max(len(lengths), 1))(*lengths)
+        self.owner._chk(self.owner.L.mi_rtj_plan_set_runs(self.h, len(lengths), arr))
+
+    def run_times(self):
+        """(ms of the run kernels summed over the decodes since profile(True), decodes that ran them)."""
+        ms, n = C.c_float(), C.c_int()
+        self.owner._chk(self.owner.L.mi_rtj_plan_run_times(self.h, C.byref(ms), C.byref(n)))
+        return float(ms.value), n.value
+
+    def run_copied(self):
+        """unchanged blocks the last decode copied from an earlier picture of their run (0: no run kernels ran)."""
+        v = C.c_longlong()
+        self.owner._chk(self.owner.L.mi_rtj_plan_run_stats(self.h, C.byref(v)))
+        return v.value
 
     def read_index(self):
         cnt = self.info()["blocks"] + self.n

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -22,6 +23,7 @@
 #include "rtj_decode_kernels.h"
 #include "rtj_encode_kernels.h"
 #include "rtj_index_kernels.h"
+#include "rtj_runs_kernels.h"
 #include "rtj_spec_kernels.h"
 #include "rtj_tables.h"
 
@@ -145,6 +147,18 @@ struct mi_rtj_plan {
   int last = 0;                            // which one the last launch wrote (mi_rtj_plan_read_index)
   std::vector<Timed> ev[MI_RTJ_NUM_KERNELS];  // one pair per launch while profiling
   int launches = 0;
+  // Runs (mi_rtj_plan_set_runs, rtj_runs_kernels.h): phase 2 resolves the unchanged blocks of pictures k > 0 of a run
+  // behind the transform.  Everything is made by set_runs; a launch only queues the three kernels.
+  int n_runs = 0;                          // runs as set (0: independent pictures)
+  uint32_t run_list = 0, run_chunks = 0;   // runs of two or more pictures / their chunks: what phase 2 covers
+  uint32_t run_nmb_max = 0;
+  RunDev* d_runs = nullptr;
+  RunChunkDev* d_run_chunks = nullptr;
+  uint64_t* d_run_mask = nullptr;          // [chunk][block]: pictures of the chunk that code the block
+  uint16_t* d_run_carry = nullptr;         // [chunk][block]: run-relative source of the chunk's first picture
+  unsigned long long* d_run_copied = nullptr;  // unchanged blocks copied by the last launch
+  bool runs_ran = false;                   // the last launch ran phase 2
+  std::vector<Timed> run_ev;               // while profiling: one per launch (b == nullptr: no phase 2 in it)
 };
 
 // One packet in flight of a pipelined session (mi_rtj_pipe_*): its own pinned staging, device packet, device
@@ -687,6 +701,28 @@ int plan_launch(mi_rtj_plan* p, const void* d_stream, void* d_out, int what = kL
     }
   }
   if ((rc = end(MI_RTJ_K_DECODE)) != MI_RTJ_OK) return rc;
+  // phase 2 of a plan with runs: unchanged blocks from the run's earlier pictures, read from this launch's index
+  const bool runs = what == kLaunchAll && p->run_chunks > 0;
+  if (p->profile) {
+    Timed rt;
+    rt.a = prev;
+    rt.owns_a = false;
+    if (runs) HIPCHK(c, hipEventCreate(&rt.b));
+    p->run_ev.push_back(rt);
+  }
+  if (runs) {
+    const unsigned bx = (unsigned)((6ull * p->run_nmb_max + kRunScanThreads - 1) / kRunScanThreads);
+    hipLaunchKernelGGL(k_runs_mask, dim3(bx, std::min(p->run_chunks, kRunMaxGridY)), dim3(kRunScanThreads), 0, ds,
+                       p->d_frames, p->d_run_chunks, p->run_chunks, (const uint32_t*)blk, p->d_run_mask);
+    hipLaunchKernelGGL(k_runs_carry, dim3(bx, std::min(p->run_list, kRunMaxGridY)), dim3(kRunScanThreads), 0, ds,
+                       p->d_runs, p->run_list, p->d_run_chunks, p->d_run_mask, p->d_run_carry, p->d_run_copied);
+    const uint32_t items = p->run_chunks * (uint32_t)kRunSubs;
+    hipLaunchKernelGGL(k_runs_copy, dim3((p->run_nmb_max + kRunTileMb - 1) / kRunTileMb, std::min(items, kRunMaxGridY)),
+                       dim3(kRunCopyThreads), 0, ds, p->d_frames, p->d_run_chunks, items, p->d_run_mask, p->d_run_carry,
+                       (uint8_t*)d_out, p->d_run_copied);
+    if (p->profile) HIPCHK(c, hipEventRecord(p->run_ev.back().b, ds));
+  }
+  if (what == kLaunchAll) p->runs_ran = runs;
   HIPCHK(c, hipGetLastError());
   if (ov) {
     HIPCHK(c, hipEventRecord(p->e_read[p->flip], ds));
@@ -982,6 +1018,12 @@ void mi_rtj_plan_destroy(mi_rtj_plan* p) {
   if (p->d_declist) (void)hipFree(p->d_declist);
   if (p->d_declist_cnt) (void)hipFree(p->d_declist_cnt);
   if (p->h_mode_seen) (void)hipHostFree(p->h_mode_seen);
+  drop_events(p->run_ev);
+  if (p->d_runs) (void)hipFree(p->d_runs);
+  if (p->d_run_chunks) (void)hipFree(p->d_run_chunks);
+  if (p->d_run_mask) (void)hipFree(p->d_run_mask);
+  if (p->d_run_carry) (void)hipFree(p->d_run_carry);
+  if (p->d_run_copied) (void)hipFree(p->d_run_copied);
   for (hipEvent_t e : p->e_read)
     if (e) (void)hipEventDestroy(e);
   delete p;
@@ -1005,6 +1047,7 @@ void mi_rtj_plan_profile(mi_rtj_plan* p, int enable) {
   if (!p) return;
   (void)hipStreamSynchronize(p->ctx->stream);
   for (auto& v : p->ev) drop_events(v);
+  drop_events(p->run_ev);
   p->profile = enable != 0;
   p->launches = 0;
 }
@@ -1036,8 +1079,10 @@ int mi_rtj_plan_step_times(mi_rtj_plan* p, float* ms, int max_steps, int* steps)
     hipEvent_t first = nullptr;
     for (int k = 0; k < MI_RTJ_NUM_KERNELS && !first; k++)
       if ((int)p->ev[k].size() > i && p->ev[k][i].owns_a) first = p->ev[k][i].a;
+    // (a launch with runs ends with phase 2)
+    hipEvent_t last = (int)p->run_ev.size() > i && p->run_ev[i].b ? p->run_ev[i].b : p->ev[MI_RTJ_K_DECODE][i].b;
     float x = 0;
-    if (first) HIPCHK(c, hipEventElapsedTime(&x, first, p->ev[MI_RTJ_K_DECODE][i].b));
+    if (first) HIPCHK(c, hipEventElapsedTime(&x, first, last));
     ms[i] = x;
   }
   return MI_RTJ_OK;
@@ -1131,6 +1176,143 @@ int mi_rtj_plan_read_index(mi_rtj_plan* p, uint32_t* dst, size_t max_entries) {
     memcpy(dst + k, all.data() + f.blk_base, cnt * sizeof(uint32_t));
     k += cnt;
   }
+  return MI_RTJ_OK;
+}
+
+namespace {
+void free_runs(mi_rtj_plan* p) {
+  if (p->d_runs) (void)hipFree(p->d_runs);
+  if (p->d_run_chunks) (void)hipFree(p->d_run_chunks);
+  if (p->d_run_mask) (void)hipFree(p->d_run_mask);
+  if (p->d_run_carry) (void)hipFree(p->d_run_carry);
+  if (p->d_run_copied) (void)hipFree(p->d_run_copied);
+  p->d_runs = nullptr;
+  p->d_run_chunks = nullptr;
+  p->d_run_mask = nullptr;
+  p->d_run_carry = nullptr;
+  p->d_run_copied = nullptr;
+  p->run_list = p->run_chunks = p->run_nmb_max = 0;
+}
+}  // namespace
+
+int mi_rtj_plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len) {
+  if (!p) return MI_RTJ_ERR_ARG;
+  mi_rtj_ctx* c = p->ctx;
+  if (n_runs < 0 || (n_runs > 0 && !run_len)) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: bad argument");
+  // ---- check everything before anything changes: a refused call leaves the plan as it was ----
+  std::vector<RunDev> runs;
+  std::vector<RunChunkDev> chunks;
+  uint64_t rows = 0, sum = 0;
+  uint32_t nmb_max = 0;
+  for (int r = 0; r < n_runs; r++) {
+    if (run_len[r] <= 0) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: run %d has length %d", r, run_len[r]);
+    sum += (uint64_t)run_len[r];
+    if (sum > (uint64_t)p->n) break;
+    const uint32_t f0 = (uint32_t)(sum - run_len[r]), len = (uint32_t)run_len[r];
+    const FrameDev& a = p->h_frames[f0];
+    std::vector<std::pair<uint64_t, uint64_t>> span;  // output pictures of the run
+    for (uint32_t k = 0; k < len; k++) {
+      const FrameDev& f = p->h_frames[f0 + k];
+      if (f.w != a.w || f.h != a.h)
+        return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: packet %u of run %d is %ux%u, the run's picture 0 is %ux%u "
+                    "(a size change inside a run is refused)", f0 + k, r, f.w, f.h, a.w, a.h);
+      span.emplace_back(f.out_off, f.out_off + (uint64_t)f.w * f.h * 3 / 2);
+    }
+    std::sort(span.begin(), span.end());
+    for (size_t k = 1; k < span.size(); k++)
+      if (span[k].first < span[k - 1].second)
+        return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: output pictures of run %d overlap", r);
+    if (len < 2) continue;  // picture 0 alone: nothing to resolve
+    RunDev rd{};
+    rd.chunk0 = (uint32_t)chunks.size();
+    rd.nmb = a.nmb;
+    for (uint32_t j = 0; j < len; j += kRunChunk) {
+      RunChunkDev ch{};
+      ch.frame0 = f0;
+      ch.rel0 = j;
+      ch.count = std::min<uint32_t>(kRunChunk, len - j);
+      ch.nmb = a.nmb;
+      ch.row = rows;
+      rows += 6ull * a.nmb;
+      chunks.push_back(ch);
+    }
+    rd.nchunks = (uint32_t)chunks.size() - rd.chunk0;
+    runs.push_back(rd);
+    nmb_max = std::max(nmb_max, a.nmb);
+  }
+  if (n_runs > 0 && sum != (uint64_t)p->n)
+    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: run lengths add up to %llu, the plan has %d packets",
+                (unsigned long long)sum, p->n);
+  if ((uint64_t)chunks.size() * kRunSubs > 0xFFFFFFFFull)
+    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: too many chunks");
+  // ---- make the new state, then swap it in (launches queued before keep using the old one until they are done) ----
+  HIPCHK(c, hipSetDevice(c->device));
+  mi_rtj_plan q;  // (only its run fields are used)
+  if (!chunks.empty()) {
+    hipError_t e = hipMalloc((void**)&q.d_runs, sizeof(RunDev) * runs.size());
+    if (e == hipSuccess) e = hipMalloc((void**)&q.d_run_chunks, sizeof(RunChunkDev) * chunks.size());
+    if (e == hipSuccess) e = hipMalloc((void**)&q.d_run_mask, sizeof(uint64_t) * rows);
+    if (e == hipSuccess) e = hipMalloc((void**)&q.d_run_carry, sizeof(uint16_t) * rows);
+    if (e == hipSuccess) e = hipMalloc((void**)&q.d_run_copied, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemcpyAsync(q.d_runs, runs.data(), sizeof(RunDev) * runs.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(q.d_run_chunks, chunks.data(), sizeof(RunChunkDev) * chunks.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(q.d_run_copied, 0, sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (the host vectors go out of scope)
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      free_runs(&q);
+      return fail(c, MI_RTJ_ERR_NOMEM, "mi_rtj_plan_set_runs: %s (%llu chunk rows of %d runs)", hipGetErrorString(e),
+                  (unsigned long long)chunks.size(), (int)runs.size());
+    }
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the old buffers may still be read by launches in flight
+  free_runs(p);
+  p->n_runs = n_runs;
+  p->d_runs = q.d_runs;
+  p->d_run_chunks = q.d_run_chunks;
+  p->d_run_mask = q.d_run_mask;
+  p->d_run_carry = q.d_run_carry;
+  p->d_run_copied = q.d_run_copied;
+  p->run_list = (uint32_t)runs.size();
+  p->run_chunks = (uint32_t)chunks.size();
+  p->run_nmb_max = nmb_max;
+  p->runs_ran = false;
+  q.d_runs = nullptr;
+  q.d_run_chunks = nullptr;
+  q.d_run_mask = nullptr;
+  q.d_run_carry = nullptr;
+  q.d_run_copied = nullptr;
+  return MI_RTJ_OK;
+}
+
+int mi_rtj_plan_run_times(mi_rtj_plan* p, float* ms, int* launches) {
+  if (!p || !ms) return MI_RTJ_ERR_ARG;
+  mi_rtj_ctx* c = p->ctx;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *ms = 0.f;
+  int n = 0;
+  for (auto& t : p->run_ev) {
+    if (!t.b) continue;
+    float x = 0;
+    HIPCHK(c, hipEventElapsedTime(&x, t.a, t.b));
+    *ms += x;
+    n++;
+  }
+  if (launches) *launches = n;
+  return MI_RTJ_OK;
+}
+
+int mi_rtj_plan_run_stats(mi_rtj_plan* p, long long* copied) {
+  if (!p || !copied) return MI_RTJ_ERR_ARG;
+  mi_rtj_ctx* c = p->ctx;
+  *copied = 0;
+  if (!p->runs_ran) return MI_RTJ_OK;
+  unsigned long long v = 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(&v, p->d_run_copied, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *copied = (long long)v;
   return MI_RTJ_OK;
 }
 

@@ -125,7 +125,9 @@ int mi_rtj_sync(mi_rtj_ctx *ctx); /* wait for everything queued on the instance'
  * to n packets in order, starting from the instance's current state, and fixes where each
  * packet lives in a device stream buffer and where its planes go in a device output buffer
  * (Y at out_offset, then U, then V, contiguous, stride = width as lib/RTjpeg.c:2708,2741 write).
- * headers: n * 12 bytes (host).  pkt_offset/pkt_len: whole packets, header included. */
+ * headers: n * 12 bytes (host).  pkt_offset/pkt_len: whole packets, header included.
+ * Packets are independent pictures: an unchanged (0xFF) block leaves its output slot as it was.  For streams with
+ * unchanged blocks, cut the plan into runs (mi_rtj_plan_set_runs below). */
 mi_rtj_plan *mi_rtj_plan_create(mi_rtj_ctx *ctx, int n, const uint8_t *headers,
                                 const uint64_t *pkt_offset, const uint32_t *pkt_len,
                                 const uint64_t *out_offset);
@@ -180,6 +182,33 @@ int mi_rtj_plan_decode_form(mi_rtj_plan *plan, int *form, int *classic_launches_
  * classic mode, i.e. on noisy content; MI_RTJ_OVERLAP=0 / 1 / 2: never / always / by that rule whatever the size), else 0.
  * Does not synchronise. */
 int mi_rtj_plan_overlapped(const mi_rtj_plan *plan);
+/* ---- runs: streams with unchanged blocks in one plan ----
+ * Without runs every packet of a plan is decoded into its own output slot and an unchanged (0xFF) block leaves that
+ * slot as it was: right for intra-only streams, and for a stream decoded one packet per plan into a slot that holds
+ * its previous picture.  A run is a stretch of consecutive packets of the plan that are consecutive pictures of ONE
+ * stream (RTjpeg_set_intra + RTjpeg_mcompress with key_rate > 0, lib/RTjpeg.c:2455-2488, 2841-2921: the output of
+ * mi_rtj_encode_stream).  Within a run:
+ *   picture 0      its unchanged blocks keep what its output slot holds (the caller prefills the slot with the
+ *                  stream's previous picture: the reference's priv->frame, lib/video_rtjpeg.c:81);
+ *   picture k > 0  an unchanged block b is block b of the nearest earlier picture j < k of the run in which b is
+ *                  coded, else block b of picture 0's slot;
+ * which is what decoding the run in order into one frame gives (lib/RTjpeg.c:2704).  One launch decodes every run:
+ * after the transform, three kernels on the instance's stream classify the blocks from the launch's block index,
+ * resolve the source picture of every unchanged block and copy it (rtj_runs_kernels.h).
+ * run_len[0..n_runs-1] cut the plan into runs in plan order; n_runs == 0 returns it to independent pictures.
+ * MI_RTJ_ERR_ARG (the plan is then unchanged and still decodes) when a length is <= 0, the lengths do not add up to the
+ * plan's packets, the packets of a run do not all have the same coded size after the plan's header logic (a size change
+ * inside a run is refused), or the output pictures of a run overlap one another.  Every buffer the runs need (about
+ * 10 bytes per block and 64 pictures of a run: 125 MB for 16,384 pictures of 1080p) is allocated here; launches allocate
+ * and synchronise nothing.  Synchronises the instance's stream. */
+int mi_rtj_plan_set_runs(mi_rtj_plan *plan, int n_runs, const int *run_len);
+/* While profiling (mi_rtj_plan_profile): device time of the run kernels summed over the decodes since profiling was
+ * switched on, *launches = decodes that ran them.  (mi_rtj_plan_times keeps its kernels; mi_rtj_plan_step_times ends
+ * a decode with runs at the end of its last run kernel.)  Synchronises the instance's stream. */
+int mi_rtj_plan_run_times(mi_rtj_plan *plan, float *ms, int *launches);
+/* Unchanged blocks (of any plane) the last decode copied from an earlier picture of their run; 0 when it ran no run
+ * kernels.  Synchronises the instance's stream. */
+int mi_rtj_plan_run_stats(mi_rtj_plan *plan, long long *copied);
 /* Test hook: copy the plan's block-start index (relative to each packet's first data byte,
  * nblocks+1 entries per frame, frames back to back) to the host after a decode. */
 int mi_rtj_plan_read_index(mi_rtj_plan *plan, uint32_t *dst, size_t max_entries);

@@ -1,13 +1,16 @@
 """Static resource and instruction-class report of the compiled gfx950 kernels.
 
-    python tools/isa_report.py [--kernel k_decode] [--cflags "..."] [--keep DIR] [--json]
+    python tools/isa_report.py [--kernel k_decode] [--cflags "..."] [--keep DIR] [--json] [--digest] [--src DIR]
 
 Compiles csrc/mi_rtjpeg.hip with -save-temps (device assembly) and prints, per kernel, what the
 code object's metadata says (VGPR / SGPR count, scalar-register spills, LDS bytes, scratch) and a
 static census of the instruction stream: vector / scalar / LDS / vector-memory instructions and —
 the figure VERDICT r2 asked to track — v_readlane_b32 / v_writelane_b32 (scalar spills are paid in
-those).  Numbers are static (program text), not dynamic counts."""
+those).  Numbers are static (program text), not dynamic counts.  --digest adds a hash of each kernel's instruction
+text (branch labels renumbered, comments dropped), so that two builds can be shown to compile a kernel to the same
+code; --src compiles another checkout's csrc/ (e.g. the parent commit's) with this tool."""
 import argparse
+import hashlib
 import json
 import os
 import re
@@ -20,12 +23,12 @@ CSRC = os.path.join(ROOT, "gmerlin-avdecoder_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
-def device_asm(cflags, keep=None):
+def device_asm(cflags, keep=None, csrc=CSRC):
     d = keep or tempfile.mkdtemp(prefix="mirtj_isa_")
     os.makedirs(d, exist_ok=True)
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-           "-save-temps"] + cflags + ["-o", os.path.join(d, "lib.so"), os.path.join(CSRC, "mi_rtjpeg.hip"),
-                                      os.path.join(CSRC, "rtj_tables.cpp")]
+           "-save-temps"] + cflags + ["-o", os.path.join(d, "lib.so"), os.path.join(csrc, "mi_rtjpeg.hip"),
+                                      os.path.join(csrc, "rtj_tables.cpp")]
     r = subprocess.run(cmd, cwd=d, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(r.stdout + r.stderr)
@@ -109,8 +112,10 @@ def parse(path):
                 c["lds"] += 1
             elif op.startswith(("global_", "buffer_", "flat_", "scratch_")):
                 c["vmem"] += 1
+        body = [re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s*;.*$", "", ln.strip())) for ln in v["lines"]]
+        digest = hashlib.sha1("\n".join(x for x in body if x).encode()).hexdigest()[:16]
         m = meta[k]
-        rep[k] = {"vgpr": int(m.get("vgpr_count", 0)), "sgpr": int(m.get("sgpr_count", 0)),
+        rep[k] = {"digest": digest, "vgpr": int(m.get("vgpr_count", 0)), "sgpr": int(m.get("sgpr_count", 0)),
                   "sgpr_spill": int(m.get("sgpr_spill_count", 0)), "vgpr_spill": int(m.get("vgpr_spill_count", 0)),
                   "lds_bytes": int(m.get("group_segment_fixed_size", 0)),
                   "scratch_bytes": int(m.get("private_segment_fixed_size", 0)), "static": c}
@@ -123,8 +128,10 @@ def main():
     ap.add_argument("--cflags", default=os.environ.get("MI_RTJ_CFLAGS", ""))
     ap.add_argument("--keep", default=None)
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--digest", action="store_true", help="print a hash of each kernel's instruction text")
+    ap.add_argument("--src", default=CSRC, help="the csrc/ directory to compile")
     a = ap.parse_args()
-    rep = parse(device_asm(a.cflags.split(), a.keep))
+    rep = parse(device_asm(a.cflags.split(), a.keep, a.src))
     names = demangle(list(rep))
     out = {}
     for k, v in rep.items():
@@ -140,7 +147,7 @@ def main():
         print(f"{k}: vgpr {v['vgpr']} sgpr {v['sgpr']} sgpr_spill {v['sgpr_spill']} vgpr_spill {v['vgpr_spill']} "
               f"lds {v['lds_bytes']} scratch {v['scratch_bytes']} | valu {c['valu']} (readlane {c['v_readlane']} "
               f"writelane {c['v_writelane']}) salu {c['salu']} smem {c['smem']} lds {c['lds']} vmem {c['vmem']} "
-              f"waitcnt {c['waitcnt']} s_nop {c['s_nop']} branch {c['branch']}")
+              f"waitcnt {c['waitcnt']} s_nop {c['s_nop']} branch {c['branch']}" + (f" | text {v['digest']}" if a.digest else ""))
 
 
 if __name__ == "__main__":
