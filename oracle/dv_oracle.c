@@ -17,7 +17,10 @@
  *                              w(h) w(2v) / 2 (2-4-8); DC 1/4
  * The fixed-point arithmetic (reconstruction multipliers with 14 fractional bits, the scaled 8-point butterfly of
  * lib/RTjpeg.c:2209-2332 with constants 362 / 473 / 669 / 277 over 256 for both transform sizes, int16 coefficients)
- * is this repository's own choice — see the header.
+ * is this repository's own choice — see the header.  That it realises the closed form above (every weight, the area
+ * limits, the class-3 doubling, the DC scale, the 2-4-8 row assignment) is checked against dv_float.c, a statement in
+ * double arithmetic with its own parser, encoder and frame writer (tests/test_dv_float_cpu.py); that check says nothing
+ * about the closed form's agreement with the standard.
  */
 #include "dv_oracle.h"
 

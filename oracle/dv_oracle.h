@@ -14,6 +14,11 @@
  * point, defined in dv_oracle.c) is this repository's own choice: a real DV decoder is free in it, and pictures of two
  * conforming decoders differ by a level or two.  Within the repository it is normative: the GPU path must reproduce
  * it bit for bit, on streams made by the encoder below and on arbitrary bytes.
+ *
+ * A second statement of the same closed form in plain double arithmetic, dv_float.h (it shares no code with this one),
+ * checks that this fixed-point arithmetic realises the weights, scales and transforms stated in dv_oracle.c's header
+ * comment, within bounds measured and recorded in tests/golden/dv_float_bounds.json.  It does not check the closed form
+ * against the standard, nor the bit layout against anything but this repository's own parsers: still parity unpinned.
  */
 #ifndef DV_ORACLE_H
 #define DV_ORACLE_H

@@ -93,14 +93,17 @@ def maps():
     return _MAPS
 
 
-def decode(frame):
-    """one 625/50 DIF frame (any 144,000 bytes) -> one picture (Y 720x576, Cb 360x288, Cr 360x288)"""
+def decode(frame, decode525=None):
+    """one 625/50 DIF frame (any 144,000 bytes) -> one picture (Y 720x576, Cb 360x288, Cr 360x288).  decode525: the
+    525/60 frame decoder the segments go through (default: the oracle's; tests/dvfloat.py passes the float statement's,
+    whose pictures are doubles)"""
+    decode525 = decode525 or D.decode
     src, dst, b625, b525 = maps()
     frame = np.ascontiguousarray(frame, np.uint8).reshape(FRAME_BYTES)
     hosts = np.zeros(HOSTS * D.FRAME_BYTES, np.uint8)
     hosts[b525] = frame[b625]
-    pics = np.concatenate([D.decode(hosts[i * D.FRAME_BYTES:(i + 1) * D.FRAME_BYTES]) for i in range(HOSTS)])
-    pic = np.empty(PICTURE_BYTES, np.uint8)
+    pics = np.concatenate([decode525(hosts[i * D.FRAME_BYTES:(i + 1) * D.FRAME_BYTES]) for i in range(HOSTS)])
+    pic = np.empty(PICTURE_BYTES, pics.dtype)
     pic[dst] = pics[src]
     return pic
 
@@ -127,16 +130,23 @@ def header(frame):
     return frame
 
 
-def encode(pic, flags=3):
-    """one 625/50 picture -> one DIF frame (the oracle's encoder on every segment, flags as dvo_encode_frame's)"""
+def pack(hosts):
+    """two 525/60 DIF frames (240,000 bytes) -> the 625/50 frame that carries their first 324 video segments"""
+    _, _, b625, b525 = maps()
+    frame = np.zeros(FRAME_BYTES, np.uint8)
+    frame[b625] = np.ascontiguousarray(hosts, np.uint8).reshape(HOSTS * D.FRAME_BYTES)[b525]
+    return header(frame)
+
+
+def encode(pic, flags=3, encode525=None):
+    """one 625/50 picture -> one DIF frame (the oracle's encoder on every segment, flags as dvo_encode_frame's).
+    encode525: another 525/60 encoder (picture, flags) -> frame whose rate control is per segment too"""
+    encode525 = encode525 or D.encode
     src, dst, b625, b525 = maps()
     pic = np.ascontiguousarray(pic, np.uint8).reshape(PICTURE_BYTES)
     pics = np.full(HOSTS * D.PICTURE_BYTES, 128, np.uint8)
     pics[src] = pic[dst]
-    hosts = np.concatenate([D.encode(pics[i * D.PICTURE_BYTES:(i + 1) * D.PICTURE_BYTES], flags) for i in range(HOSTS)])
-    frame = np.zeros(FRAME_BYTES, np.uint8)
-    frame[b625] = hosts[b525]
-    return header(frame)
+    return pack(np.concatenate([encode525(pics[i * D.PICTURE_BYTES:(i + 1) * D.PICTURE_BYTES], flags) for i in range(HOSTS)]))
 
 
 def synth625(n, seed=1, amp=8):

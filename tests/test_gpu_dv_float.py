@@ -1,0 +1,103 @@
+"""The DV kernel (libmi_dv.so through its C ABI) against the floating-point statement oracle/dv_float.c directly, on
+streams no other GPU test decodes: frames of the plain encoder (family b) and symbol-written frames (family c), for
+525/60 and 625/50, next to the oracle's own (family a).  Every decoded picture is compared twice: bit for bit with the
+oracle (the existing contract), and with dvf_decode_frame within the bound recorded in
+tests/golden/dv_float_bounds.json — the same number as on the CPU, no margin, because the kernel has to equal the
+oracle.  PARITY UNPINNED: this pins the kernel's arithmetic to the closed form, not the closed form to the standard."""
+import importlib
+
+import numpy as np
+import pytest
+
+import dv625 as P
+import dvfloat as F
+import dvlib as D
+
+pytestmark = pytest.mark.gpu
+B = F.bounds()
+
+
+@pytest.fixture(scope="module")
+def dv():
+    return importlib.import_module("gmerlin-avdecoder_amd.dv")
+
+
+@pytest.fixture(scope="module")
+def dev(dv):
+    d = dv.MiDv(0)
+    yield d
+    d.close()
+
+
+def _sys(dv, system):
+    return dv.SYS_525_60 if system == 525 else dv.SYS_625_50
+
+
+def check(system, family, frame, got):
+    """one decoded picture: the oracle's bit for bit, and the float statement's within the family's bound on every block"""
+    want = F.oracle_decode(system, frame)
+    if not np.array_equal(got, want):
+        bad = np.flatnonzero(got != want)
+        raise AssertionError(f"{system} {family}: {bad.size} bytes differ from the oracle, first at {bad[0]} (got {got[bad[0]]}, want {want[bad[0]]})")
+    pic, out, _ = F.float_decode_info(system, frame)
+    assert out == 0, f"{out} blocks outside the fixed-point range"
+    d = F.deviation(got, pic)
+    b = B["bounds"]["frames"][str(system)][family]
+    print(system, family, float(np.abs(d).max()), float(d.mean()))
+    assert np.abs(d).max() <= b["abs"], (system, family, float(np.abs(d).max()), int(np.abs(d).argmax()))
+    assert abs(d.mean()) <= b["mean"], (system, family, float(d.mean()))
+
+
+@pytest.mark.parametrize("system", [525, 625])
+@pytest.mark.parametrize("family", ["b", "c"])
+def test_plain_encoder_and_symbol_written_frames(dev, dv, system, family):
+    frames = F.frames(system, family)
+    got = dev.decode_frames(np.stack(frames), system=_sys(dv, system))
+    for f, g in zip(frames, got):
+        check(system, family, f, g)
+
+
+@pytest.mark.parametrize("system", [525, 625])
+def test_a_batch_of_all_three_families_and_the_one_frame_entry_point(dev, dv, system):
+    mixed = []
+    for i in range(2):
+        mixed += [(fam, F.frames(system, fam)[-1 - i]) for fam in "abc"]
+    got = dev.decode_frames(np.stack([f for _, f in mixed]), system=_sys(dv, system))
+    for (fam, f), g in zip(mixed, got):
+        check(system, fam, f, g)
+    for fam, f in mixed[1:3]:
+        check(system, fam, f, np.concatenate(dev.decode_frame(f, system=_sys(dv, system))))
+
+
+@pytest.mark.parametrize("system", [525, 625])
+def test_every_scan_positions_gain_on_the_kernel(dev, dv, system):
+    """one symbol-written frame whose blocks are single large coefficients: (scan position, class, qno, mode) walks all
+    8,064 combinations over the frame's 8,100 blocks (625/50: the same segments in a 625/50 frame).  Pixels within the
+    bound and least-squares gain within the relative bound of the float pattern, in one launch; the message names the
+    position."""
+    dif, order = F.sweep_frame()
+    inputs = F.position_sweep()
+    if system == 525:
+        got = dev.decode_frames(dif[None])[0]
+        assert np.array_equal(got, D.decode(dif))
+        pic525 = got
+    else:
+        frame = P.pack(np.concatenate([dif, dif]))
+        got = dev.decode_frames(frame[None], system=dv.SYS_625_50)[0]
+        assert np.array_equal(got, P.decode(frame))
+        src, dst, _, _ = P.maps()
+        hosts = np.zeros(P.HOSTS * D.PICTURE_BYTES, np.uint8)
+        hosts[src] = got[dst]
+        pic525 = hosts[:D.PICTURE_BYTES]
+    px = np.zeros((order.size, 64), np.uint8)
+    px[order] = F.block_pixels(pic525)[:order.size]
+    m = F.measure_blocks(inputs, got=px)
+    print(m)
+    b = B["bounds"]["blocks"]["position"]
+    mode, k, cls, qno = F.sweep_index()
+
+    def blame(i):
+        return f"mode {mode[i]}, scan position {k[i]}, class {cls[i]}, qno {qno[i]}"
+    assert m["gain"] <= b["gain"], f"gain off by {m['gain']:.4f} at {blame(m['gain_at'])}"
+    assert m["abs"] <= b["abs"], f"{m['abs']:.3f} levels at {blame(m['abs_at'])}"
+    assert np.array_equal(F.block_pixels(pic525)[order.size:], np.full((F.BLOCKS - order.size, 64), 128))  # the flat rest
