@@ -20,6 +20,7 @@ typedef enum { GAVL_SOURCE_EOF = 0, GAVL_SOURCE_OK = 1, GAVL_SOURCE_AGAIN = 2 } 
 #define GAVL_MAX_PLANES 4
 #define GAVL_YUV_420_P 0x0501 /* opaque tag here */
 #define GAVL_YUV_411_P 0x0505 /* opaque tag here */
+#define GAVL_YUV_422_P 0x0502 /* opaque tag here */
 #define GAVL_META_FORMAT "Format"
 #define GAVL_LOG_ERROR 1
 #define GAVL_LOG_INFO 4

@@ -1,5 +1,5 @@
-// dv_common.h — what the host side and the gfx950 kernels of the DV25 decoder share: the constant tables and the
-// two systems' frame and picture layouts.
+// dv_common.h — what the host side and the gfx950 kernels of the DV decoder share: the constant tables and the
+// four systems' frame and picture layouts (25 Mbit/s: 525/60 4:1:1, 625/50 4:2:0; 50 Mbit/s: both in 4:2:2).
 #pragma once
 #include <stdint.h>
 
@@ -56,7 +56,7 @@ constexpr int kSegments = 270;  // video segments per frame: 10 DIF sequences of
     (y8) = (x32) > 21u ? 2u * serp_ + 6u * i_ : serp_ + 6u * i_;                              \
   } while (0)
 struct Sys525 {
-  static constexpr int kId = 0;
+  static constexpr int kId = 0, kChans = 1;
   static constexpr int kFrameBytes = 120000, kSeqs = 10, kSegments = kSeqs * 27, kPairs = kSegments / 2;
   static constexpr int kW = 720, kH = 480, kCW = 180, kCH = 480, kPicBytes = kW * kH + 2 * kCW * kCH;
   static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x32, uint32_t& y8) {
@@ -69,7 +69,7 @@ struct Sys525 {
 // super block (row (seq + {2,6,8,0,4}[m]) mod 12, column {2,1,3,0,4}[m]), inside it column slot / 3 and row slot % 3,
 // upwards in odd columns.  x, y in 16-pixel units (0..44, 0..35).
 struct Sys625 {
-  static constexpr int kId = 1;
+  static constexpr int kId = 1, kChans = 1;
   static constexpr int kFrameBytes = 144000, kSeqs = 12, kSegments = kSeqs * 27, kPairs = kSegments / 2;
   static constexpr int kW = 720, kH = 576, kCW = 360, kCH = 288, kPicBytes = kW * kH + 2 * kCW * kCH;
   static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x16, uint32_t& y16) {
@@ -81,9 +81,38 @@ struct Sys625 {
     y16 = 3u * row + (c & 1u ? 2u - r : r);
   }
 };
+
+// ---- the two 50 Mbit/s systems ("DVCPRO50", VAUX stype 4; SMPTE 314M as this repository reads it: parity unpinned) ----
+// Two DIF channels back to back, each of kSeqs sequences laid out as above; the compressed macroblock is the 25 Mbit/s
+// one, but its areas 1 and 3 carry no pixels (they are parsed and lend their unused bits; their coefficients are thrown
+// away): area 0 is the left 8 x 8 luma block, area 2 the right one, area 4 Cr, area 5 Cb.  A macroblock is 16 pixels wide
+// and 8 lines high; the picture is 45 x (kH / 8) of them, Cb / Cr 360 x kH.  place() takes `seq` as the frame's sequence
+// in byte order, 0 .. 2 kSeqs - 1 (channel seq / kSeqs), and is Sys625::place with the super-block row 2 row + channel
+// and rows of 8 lines: x in 16-pixel columns (0..44), y in 8-line rows (0..59 / 0..71).
+template <int Id, int Seqs>
+struct Sys422 {
+  static constexpr int kId = Id, kChans = 2;
+  static constexpr int kSeqs = Seqs, kFrameBytes = kChans * kSeqs * 150 * 80, kSegments = kChans * kSeqs * 27, kPairs = kSegments / 2;
+  static constexpr int kW = 720, kH = 48 * kSeqs, kCW = 360, kCH = kH, kPicBytes = kW * kH + 2 * kCW * kCH;
+  static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x16, uint32_t& y8) {
+    const uint32_t off = m == 0u ? 2u : m == 1u ? 6u : m == 2u ? 8u : m == 3u ? 0u : 4u;
+    const uint32_t col = m == 0u ? 2u : m == 1u ? 1u : m == 2u ? 3u : m == 3u ? 0u : 4u;
+    const uint32_t chan = seq >= (uint32_t)kSeqs ? 1u : 0u;
+    const uint32_t row = (seq - chan * (uint32_t)kSeqs + off) % (uint32_t)kSeqs;
+    const uint32_t c = slot / 3u, r = slot - 3u * c;
+    x16 = 9u * col + c;
+    y8 = 3u * (2u * row + chan) + (c & 1u ? 2u - r : r);
+  }
+};
+using Sys525_422 = Sys422<4, 10>;  // 240,000-byte frames, 720 x 480
+using Sys625_422 = Sys422<5, 12>;  // 288,000-byte frames, 720 x 576
 static_assert(Sys525::kFrameBytes == Sys525::kSeqs * 150 * 80 && Sys625::kFrameBytes == Sys625::kSeqs * 150 * 80, "DIF frames");
 static_assert(Sys525::kPicBytes == kPicBytes && Sys525::kFrameBytes == kFrameBytes && Sys525::kSegments == kSegments, "525/60");
 static_assert(Sys625::kPicBytes == 622080 && Sys625::kPairs * 2 == Sys625::kSegments, "625/50");
+static_assert(Sys525_422::kFrameBytes == 240000 && Sys525_422::kH == 480 && Sys525_422::kPicBytes == 691200 &&
+                  Sys525_422::kSegments == 540 && Sys525_422::kPairs == 270, "525/60 4:2:2");
+static_assert(Sys625_422::kFrameBytes == 288000 && Sys625_422::kH == 576 && Sys625_422::kPicBytes == 829440 &&
+                  Sys625_422::kSegments == 648 && Sys625_422::kPairs == 324, "625/50 4:2:2");
 
 // builds the tables (dv_tables.cpp); false if the code's lengths are not a complete prefix code
 bool build_tables(Tables* t);

@@ -1,9 +1,10 @@
-// dv_decode_kernels.h — gfx950 kernel of the DV25 video decoder, 525/60 4:1:1 and 625/50 4:2:0 (the arithmetic: DESIGN.md
-// section 9; the format: IEC 61834-2 / SMPTE 314M; nothing in the reference to follow — lib/dvframe.c:663-676 passes the
-// DIF frame on).
+// dv_decode_kernels.h — gfx950 kernel of the DV video decoder: 525/60 4:1:1 and 625/50 4:2:0 at 25 Mbit/s, both line
+// systems in 4:2:2 at 50 Mbit/s (the arithmetic: DESIGN.md section 9; the format: IEC 61834-2 / SMPTE 314M; nothing in
+// the reference to follow — lib/dvframe.c:663-676 passes the DIF frame on).
 //
-//   k_dv_decode<Sys>  one instantiation per system (dv_common.h: Sys525, Sys625), which differ only in the frame's
-//                  sequence count, the macroblock shuffle and where a block's pixels go.
+//   k_dv_decode<Sys>  one instantiation per system (dv_common.h: Sys525, Sys625, Sys525_422, Sys625_422), which differ
+//                  only in the frame's sequence count, the macroblock shuffle, where a block's pixels go and, for the
+//                  4:2:2 systems, in which areas carry pixels at all (areas 1 and 3 are parsed and dropped).
 //                  One wave per two video segments (2 x 5 compressed macroblocks = 60 blocks, one lane each):
 //                  the three passes of the variable-length decode, reconstruction, both inverse transforms, placement.
 //                  A workgroup is kDvWaves such waves that share the constant tables in LDS and nothing else: the only
@@ -376,8 +377,12 @@ __global__ __launch_bounds__(64 * kDvWaves) void k_dv_decode(const uint8_t* __re
 #pragma unroll
     for (int i = 0; i < 8; i++) q[i] = qq[i];
   }
-  const bool pk = __all(!live || mirtj::pk_range_full(q, K));
-  if (!live || (MIDV_SKIP & 2)) return;
+  // (4:2:2: areas 1 and 3 carry no pixels.  Their lanes ran all three passes, since their bits are the macroblock's and
+  // the segment's like any block's; here they vote like idle lanes, whatever their scratch holds, and leave)
+  constexpr bool k422 = Sys::kChans == 2;
+  const bool shown = live && !(k422 && (j == 1u || j == 3u));
+  const bool pk = __all(!shown || mirtj::pk_range_full(q, K));
+  if (!shown || (MIDV_SKIP & 2)) return;
   // where the block goes (the system's macroblock shuffling and placement)
   uint32_t mx, my8;
   if constexpr (Sys::kId == Sys525::kId)
@@ -399,6 +404,15 @@ __global__ __launch_bounds__(64 * kDvWaves) void k_dv_decode(const uint8_t* __re
       org = kW * kH + (j == 4u ? kCW * kH : 0u) + 8u * y8 * kCW + 8u * x32;  // block 4 is Cr (third plane), block 5 Cb
     }
     halves = j >= 4u && edge;  // the right-edge chroma block: left half here, right half eight lines below
+  } else if constexpr (k422) {  // 4:2:2: 16 x 8 macroblocks (mx: 16-pixel column, my8: 8-line row), whole 8-byte rows
+    constexpr uint32_t W = Sys::kW, H = Sys::kH, CW = Sys::kCW, CH = Sys::kCH;
+    if (j < 4u) {  // areas 0 and 2: the left and the right luma block
+      stride = W;
+      org = 8u * my8 * W + 16u * mx + 8u * (j >> 1);
+    } else {
+      stride = CW;
+      org = W * H + (j == 4u ? CW * CH : 0u) + 8u * my8 * CW + 8u * mx;  // block 4 is Cr (third plane), block 5 Cb
+    }
   } else {  // 625/50: 16 x 16 macroblocks everywhere (mx, my8: their column and row), whole 8-byte rows
     constexpr uint32_t W = Sys::kW, H = Sys::kH, CW = Sys::kCW, CH = Sys::kCH;
     const uint32_t x16 = mx, y16 = my8;

@@ -1,5 +1,5 @@
-// mi_dv.hip — C ABI (include/mi_dv.h) of the MI355X DV25 decoder (525/60 4:1:1, 625/50 4:2:0).  No CPU path: without a gfx950 device
-// every call fails with a message.
+// mi_dv.hip — C ABI (include/mi_dv.h) of the MI355X DV decoder (25 Mbit/s: 525/60 4:1:1, 625/50 4:2:0; 50 Mbit/s: both
+// line systems in 4:2:2).  No CPU path: without a gfx950 device every call fails with a message.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -21,6 +21,15 @@ static_assert(MI_DV_625_FRAME_BYTES == Sys625::kFrameBytes && MI_DV_625_PICTURE_
                   MI_DV_625_HEIGHT == Sys625::kH && MI_DV_625_CHROMA_WIDTH == Sys625::kCW &&
                   MI_DV_625_CHROMA_HEIGHT == Sys625::kCH && MI_DV_SYS_525_60 == Sys525::kId && MI_DV_SYS_625_50 == Sys625::kId,
               "header and kernels agree (625/50)");
+static_assert(MI_DV_SYS_525_60_422 == Sys525_422::kId && MI_DV_525_422_FRAME_BYTES == Sys525_422::kFrameBytes &&
+                  MI_DV_525_422_PICTURE_BYTES == Sys525_422::kPicBytes && MI_DV_HEIGHT == Sys525_422::kH &&
+                  MI_DV_SYS_625_50_422 == Sys625_422::kId && MI_DV_625_422_FRAME_BYTES == Sys625_422::kFrameBytes &&
+                  MI_DV_625_422_PICTURE_BYTES == Sys625_422::kPicBytes && MI_DV_625_HEIGHT == Sys625_422::kH &&
+                  MI_DV_422_CHROMA_WIDTH == Sys525_422::kCW && MI_DV_422_CHROMA_WIDTH == Sys625_422::kCW &&
+                  Sys525_422::kCH == Sys525_422::kH && Sys625_422::kCH == Sys625_422::kH && MI_DV_WIDTH == Sys525_422::kW &&
+                  MI_DV_WIDTH == Sys625_422::kW,
+              "header and kernels agree (4:2:2)");
+static_assert(MI_DV_SYS_525_60_422 == (0x4 | 0) && MI_DV_SYS_625_50_422 == (0x4 | 1), "4:2:2 system = stype | DSF");
 
 namespace {
 std::mutex g_mu;
@@ -33,11 +42,11 @@ struct mi_dv_ctx {
   Tables* d_tab = nullptr;
   // one pair of events around every launch since the last mi_dv_kernel_times (recycled there)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_used, ev_free;
-  // the one-frame path's buffers (525/60 sizes, or 625/50 ones once a 625/50 frame came: big enough for both)
+  // the one-frame path's buffers: as large as the largest system this instance has seen needs them
   uint8_t* d_frame = nullptr;
   uint8_t* d_pic = nullptr;
   uint8_t* h_pic = nullptr;  // pinned
-  bool one_625 = false;
+  size_t cap_frame = 0, cap_pic = 0;
   std::string err;
 };
 
@@ -204,6 +213,48 @@ int launch(mi_dv_ctx* c, const char* who, const void* d_frames, int n, void* d_p
   DVCHK(c, hipEventRecord(ev.second, c->stream));
   return MI_DV_OK;
 }
+
+// the one-frame path's buffers hold a frame and a picture of these sizes (they only grow; the stream is idle between calls)
+int one_frame_buffers(mi_dv_ctx* c, size_t frame_bytes, size_t pic_bytes) {
+  if (frame_bytes > c->cap_frame) {
+    if (c->d_frame) DVCHK(c, hipFree(c->d_frame));
+    c->d_frame = nullptr;
+    c->cap_frame = 0;
+    DVCHK(c, hipMalloc((void**)&c->d_frame, frame_bytes));
+    c->cap_frame = frame_bytes;
+  }
+  if (pic_bytes > c->cap_pic) {
+    if (c->d_pic) DVCHK(c, hipFree(c->d_pic));
+    if (c->h_pic) DVCHK(c, hipHostFree(c->h_pic));
+    c->d_pic = c->h_pic = nullptr;
+    c->cap_pic = 0;
+    DVCHK(c, hipMalloc((void**)&c->d_pic, pic_bytes));
+    DVCHK(c, hipHostMalloc((void**)&c->h_pic, pic_bytes, hipHostMallocDefault));
+    c->cap_pic = pic_bytes;
+  }
+  return MI_DV_OK;
+}
+
+// one checked host frame of system S through the kernel into the caller's planes
+template <class S>
+int decode_one(mi_dv_ctx* c, const char* who, const uint8_t* frame, uint8_t* const planes[3], const int strides[3]) {
+  if (strides[0] < S::kW || strides[1] < S::kCW || strides[2] < S::kCW) return fail(c, MI_DV_ERR_ARG, "strides below the picture's width");
+  DVCHK(c, hipSetDevice(c->device));
+  int rc = one_frame_buffers(c, S::kFrameBytes, S::kPicBytes);
+  if (rc != MI_DV_OK) return rc;
+  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, S::kFrameBytes, hipMemcpyHostToDevice, c->stream));
+  rc = launch<S>(c, who, c->d_frame, 1, c->d_pic);
+  if (rc != MI_DV_OK) return rc;
+  DVCHK(c, hipMemcpyAsync(c->h_pic, c->d_pic, S::kPicBytes, hipMemcpyDeviceToHost, c->stream));
+  DVCHK(c, hipStreamSynchronize(c->stream));
+  const uint8_t* src = c->h_pic;
+  for (int pl = 0; pl < 3; pl++) {
+    const int w = pl ? S::kCW : S::kW, h = pl ? S::kCH : S::kH;
+    for (int y = 0; y < h; y++) memcpy(planes[pl] + (size_t)y * strides[pl], src + (size_t)y * w, (size_t)w);
+    src += (size_t)w * h;
+  }
+  return MI_DV_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -215,6 +266,8 @@ int mi_dv_decode_batch(mi_dv_ctx* c, const void* d_frames, int n, void* d_pics) 
 int mi_dv_decode_batch_sys(mi_dv_ctx* c, int system, const void* d_frames, int n, void* d_pics) {
   if (system == MI_DV_SYS_525_60) return launch<Sys525>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
   if (system == MI_DV_SYS_625_50) return launch<Sys625>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
+  if (system == MI_DV_SYS_525_60_422) return launch<Sys525_422>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
+  if (system == MI_DV_SYS_625_50_422) return launch<Sys625_422>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
   return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_batch_sys: unknown system %d", system);
 }
 
@@ -249,81 +302,70 @@ int mi_dv_decode_frame(mi_dv_ctx* c, const uint8_t* frame, size_t len, uint8_t* 
   // dv_frame_profile (lib/dvframe.c:298-316): DSF = byte 3 bit 7, stype = byte 80*5+48+3 & 0x1f; only 525/60 25 Mbit/s here
   if ((frame[3] & 0x80) || (frame[80 * 5 + 48 + 3] & 0x1f) != 0)
     return fail(c, MI_DV_ERR_FORMAT, "not a 525/60 25 Mbit/s DV frame (DSF %d, stype 0x%02x)", frame[3] >> 7, frame[80 * 5 + 48 + 3] & 0x1f);
-  if (strides[0] < kW || strides[1] < kCW || strides[2] < kCW) return fail(c, MI_DV_ERR_ARG, "strides below the picture's width");
-  DVCHK(c, hipSetDevice(c->device));
-  if (!c->d_frame) {
-    DVCHK(c, hipMalloc((void**)&c->d_frame, kFrameBytes));
-    DVCHK(c, hipMalloc((void**)&c->d_pic, kPicBytes));
-    DVCHK(c, hipHostMalloc((void**)&c->h_pic, kPicBytes, hipHostMallocDefault));
-  }
-  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, kFrameBytes, hipMemcpyHostToDevice, c->stream));
-  const int rc = mi_dv_decode_batch(c, c->d_frame, 1, c->d_pic);
-  if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipMemcpyAsync(c->h_pic, c->d_pic, kPicBytes, hipMemcpyDeviceToHost, c->stream));
-  DVCHK(c, hipStreamSynchronize(c->stream));
-  const uint8_t* src = c->h_pic;
-  for (int pl = 0; pl < 3; pl++) {
-    const int w = pl ? kCW : kW;
-    for (int y = 0; y < kH; y++) memcpy(planes[pl] + (size_t)y * strides[pl], src + (size_t)y * w, (size_t)w);
-    src += (size_t)w * kH;
-  }
-  return MI_DV_OK;
+  return decode_one<Sys525>(c, "mi_dv_decode_frame", frame, planes, strides);
 }
 
 int mi_dv_system_of(const uint8_t* frame, size_t len) {
   // dv_frame_profile (lib/dvframe.c:298-316): DSF = byte 3 bit 7, APT = byte 5 & 7, stype = byte 80*5+48+3 & 0x1f
   if (!frame || len < 80 * 6) return -1;
   const int dsf = frame[3] >> 7, apt = frame[5] & 7, stype = frame[80 * 5 + 48 + 3] & 0x1f;
-  if (stype != 0) return -1;  // DVCPRO50 and the HD profiles
+  if (stype != 0) return -1;  // DVCPRO50 (mi_dv_profile_of knows it) and the HD profiles
   if (dsf == 0) return len >= (size_t)Sys525::kFrameBytes ? MI_DV_SYS_525_60 : -1;
   if (apt != 0) return -1;  // DVCPRO 625/50 4:1:1 (lib/dvframe.c:303)
   return len >= (size_t)Sys625::kFrameBytes ? MI_DV_SYS_625_50 : -1;
 }
 
+int mi_dv_profile_of(const uint8_t* frame, size_t len) {
+  if (!frame || len < 80 * 6) return -1;
+  const int dsf = frame[3] >> 7, stype = frame[80 * 5 + 48 + 3] & 0x1f;
+  if (stype == 0x4) {  // DVCPRO50: two DIF channels, 4:2:2 (lib/dvframe.c:170-211)
+    if (dsf == 0) return len >= (size_t)Sys525_422::kFrameBytes ? MI_DV_SYS_525_60_422 : -1;
+    return len >= (size_t)Sys625_422::kFrameBytes ? MI_DV_SYS_625_50_422 : -1;
+  }
+  return mi_dv_system_of(frame, len);
+}
+
 int mi_dv_decode_frame_sys(mi_dv_ctx* c, int system, const uint8_t* frame, size_t len, uint8_t* const planes[3],
                            const int strides[3]) {
   if (system == MI_DV_SYS_525_60) return mi_dv_decode_frame(c, frame, len, planes, strides);
-  if (system != MI_DV_SYS_625_50) return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame_sys: unknown system %d", system);
-  using S = Sys625;
+  if (system != MI_DV_SYS_625_50 && system != MI_DV_SYS_525_60_422 && system != MI_DV_SYS_625_50_422)
+    return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame_sys: unknown system %d", system);
   if (!c || !frame || !planes || !strides || !planes[0] || !planes[1] || !planes[2])
     return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame_sys: NULL argument");
-  if (len < (size_t)S::kFrameBytes) return fail(c, MI_DV_ERR_FORMAT, "DIF frame of %zu bytes: 625/50 frames have %d", len, S::kFrameBytes);
-  if (mi_dv_system_of(frame, len) != MI_DV_SYS_625_50)
-    return fail(c, MI_DV_ERR_FORMAT, "not a 625/50 25 Mbit/s 4:2:0 DV frame (DSF %d, APT %d, stype 0x%02x)", frame[3] >> 7,
-                frame[5] & 7, frame[80 * 5 + 48 + 3] & 0x1f);
-  if (strides[0] < S::kW || strides[1] < S::kCW || strides[2] < S::kCW) return fail(c, MI_DV_ERR_ARG, "strides below the picture's width");
-  DVCHK(c, hipSetDevice(c->device));
-  if (!c->one_625) {  // once per instance: replaces the 525/60-sized buffers (the stream is idle between calls)
-    if (c->d_frame) DVCHK(c, hipFree(c->d_frame));
-    if (c->d_pic) DVCHK(c, hipFree(c->d_pic));
-    if (c->h_pic) DVCHK(c, hipHostFree(c->h_pic));
-    c->d_frame = c->d_pic = c->h_pic = nullptr;
-    DVCHK(c, hipMalloc((void**)&c->d_frame, S::kFrameBytes));
-    DVCHK(c, hipMalloc((void**)&c->d_pic, S::kPicBytes));
-    DVCHK(c, hipHostMalloc((void**)&c->h_pic, S::kPicBytes, hipHostMallocDefault));
-    c->one_625 = true;
+  if (system == MI_DV_SYS_625_50) {
+    using S = Sys625;
+    if (len < (size_t)S::kFrameBytes) return fail(c, MI_DV_ERR_FORMAT, "DIF frame of %zu bytes: 625/50 frames have %d", len, S::kFrameBytes);
+    if (mi_dv_system_of(frame, len) != MI_DV_SYS_625_50)
+      return fail(c, MI_DV_ERR_FORMAT, "not a 625/50 25 Mbit/s 4:2:0 DV frame (DSF %d, APT %d, stype 0x%02x)", frame[3] >> 7,
+                  frame[5] & 7, frame[80 * 5 + 48 + 3] & 0x1f);
+    return decode_one<S>(c, "mi_dv_decode_frame_sys", frame, planes, strides);
   }
-  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, S::kFrameBytes, hipMemcpyHostToDevice, c->stream));
-  const int rc = launch<S>(c, "mi_dv_decode_frame_sys", c->d_frame, 1, c->d_pic);
-  if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipMemcpyAsync(c->h_pic, c->d_pic, S::kPicBytes, hipMemcpyDeviceToHost, c->stream));
-  DVCHK(c, hipStreamSynchronize(c->stream));
-  const uint8_t* src = c->h_pic;
-  for (int pl = 0; pl < 3; pl++) {
-    const int w = pl ? S::kCW : S::kW, h = pl ? S::kCH : S::kH;
-    for (int y = 0; y < h; y++) memcpy(planes[pl] + (size_t)y * strides[pl], src + (size_t)y * w, (size_t)w);
-    src += (size_t)w * h;
-  }
-  return MI_DV_OK;
+  // the 50 Mbit/s systems: DSF = byte 3 bit 7, stype = byte 80*5+48+3 & 0x1f must be 0x4 (lib/dvframe.c:298-316)
+  const bool pal = system == MI_DV_SYS_625_50_422;
+  const char* name = pal ? "625/50" : "525/60";
+  const int need = pal ? Sys625_422::kFrameBytes : Sys525_422::kFrameBytes;
+  if (len < (size_t)need)
+    return fail(c, MI_DV_ERR_FORMAT, "DIF frame of %zu bytes: %s 50 Mbit/s 4:2:2 frames have %d", len, name, need);
+  if (mi_dv_profile_of(frame, len) != system)
+    return fail(c, MI_DV_ERR_FORMAT, "not a %s 50 Mbit/s 4:2:2 DV frame of %d bytes (DSF %d, stype 0x%02x; expected DSF %d, stype 0x04)",
+                name, need, frame[3] >> 7, frame[80 * 5 + 48 + 3] & 0x1f, pal ? 1 : 0);
+  if (pal) return decode_one<Sys625_422>(c, "mi_dv_decode_frame_sys", frame, planes, strides);
+  return decode_one<Sys525_422>(c, "mi_dv_decode_frame_sys", frame, planes, strides);
 }
 
 int mi_dv_mb_place(int system, int seq, int slot, int m, int* x, int* y) {
-  const int seqs = system == MI_DV_SYS_525_60 ? Sys525::kSeqs : system == MI_DV_SYS_625_50 ? Sys625::kSeqs : 0;
+  const int seqs = system == MI_DV_SYS_525_60       ? Sys525::kSeqs
+                   : system == MI_DV_SYS_625_50     ? Sys625::kSeqs
+                   : system == MI_DV_SYS_525_60_422 ? 2 * Sys525_422::kSeqs  // (both channels' sequences, in byte order)
+                   : system == MI_DV_SYS_625_50_422 ? 2 * Sys625_422::kSeqs
+                                                    : 0;
   if (!x || !y || seq < 0 || seq >= seqs || slot < 0 || slot >= 27 || m < 0 || m >= 5)
     return fail(nullptr, MI_DV_ERR_ARG, "mi_dv_mb_place: system %d, sequence %d, segment %d, macroblock %d out of range", system, seq, slot, m);
   uint32_t ux, uy;
   if (system == MI_DV_SYS_525_60) Sys525::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
-  else Sys625::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
+  else if (system == MI_DV_SYS_625_50) Sys625::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
+  else if (system == MI_DV_SYS_525_60_422) Sys525_422::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
+  else Sys625_422::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
   *x = (int)ux;
   *y = (int)uy;
   return MI_DV_OK;

@@ -1,16 +1,18 @@
 /*
- * video_dv_mi355x.c — a bgav_video_decoder_t for DV25 video on an MI355X: 525/60 (NTSC, 4:1:1) and 625/50 (PAL) in
- * the IEC 4:2:0 profile.
+ * video_dv_mi355x.c — a bgav_video_decoder_t for DV video on an MI355X: at 25 Mbit/s 525/60 (NTSC, 4:1:1) and 625/50
+ * (PAL) in the IEC 4:2:0 profile, at 50 Mbit/s (DVCPRO50) both line systems in 4:2:2.
  *
  * In gmerlin-avdecoder DV pixels are libavcodec's: lib/dvframe.c:663-676 hands each 120,000-byte DIF frame on as a
  * video packet, and the "FFmpeg DV decoder" entry of lib/video_ffmpeg.c:1572-1575 decodes it for the fourccs of
  * lib/video.c:122-145 (bgav_dv_fourccs).  This file registers a decoder for the same fourccs that is asked FIRST
  * (first match wins, lib/codecs.c:246-279): its .probe accepts a stream only when a gfx950 device is usable and the
- * stream is 720 x 480, or 720 x 576 with the pixel format GAVL_YUV_420_P.  The demultiplexer sets that pixel format
- * from the DIF profile (lib/dvframe.c:490-500; lib/parse_dv.c:51 for DV in other containers), so a 625/50 stream is
- * ours only in the IEC 4:2:0 profile.  Every other DV flavour (DVCPRO 625/50 4:1:1, a 720 x 576 stream whose pixel
- * format is not known, DVCPRO50, DVCPRO HD) and every host without the device still go to the FFmpeg decoder.  The
- * pixels come from include/mi_dv.h: mi_dv_decode_frame_sys with the system the stream was opened with.
+ * stream is 720 x 480, or 720 x 576 with the pixel format GAVL_YUV_420_P or GAVL_YUV_422_P.  The demultiplexer sets
+ * the pixel format from the DIF profile (lib/dvframe.c:490-500; lib/parse_dv.c:51 for DV in other containers): a stream
+ * of either height with GAVL_YUV_422_P is DVCPRO50 and decodes to 4:2:2 pictures; a 720 x 480 stream with any other or no
+ * pixel format is 525/60 4:1:1; a 625/50 stream at 25 Mbit/s is ours only in the IEC 4:2:0 profile.  Every other DV
+ * flavour (DVCPRO 625/50 4:1:1, a 720 x 576 stream whose pixel format is not known, DVCPRO HD) and every host without
+ * the device still go to the FFmpeg decoder.  The pixels come from include/mi_dv.h: mi_dv_decode_frame_sys with the
+ * system the stream was opened with.
  *
  * Integration: add this file to lib/Makefile.am, declare
  * bgav_init_video_decoders_dv_mi355x() in include/codecs.h and call it in bgav_codecs_init (lib/codecs.c:160-200) BEFORE
@@ -33,7 +35,7 @@
 
 typedef struct {
   mi_dv_ctx *ctx;
-  int system; /* MI_DV_SYS_525_60 or MI_DV_SYS_625_50, from the stream's format */
+  int system; /* MI_DV_SYS_*, from the stream's format */
 } dv_hip_priv_t;
 
 /* the fourccs of lib/video.c:122-145; inside the tree the library's own array is used */
@@ -48,9 +50,15 @@ static const uint32_t dv_fourccs[] = {
 #define DV_FOURCCS bgav_dv_fourccs /* include/avdec_private.h:1435 */
 #endif
 
-/* the system of a stream by its format: 720 x 480 is 525/60; 720 x 576 is 625/50 only in the 4:2:0 profile; -1 else */
+/* the system of a stream by its format: GAVL_YUV_422_P is the 50 Mbit/s system of the stream's height; otherwise
+ * 720 x 480 is 525/60 4:1:1 and 720 x 576 is 625/50 only in the 4:2:0 profile; -1 else */
 static int dv_system(const gavl_video_format_t *fmt) {
   if (!fmt || fmt->image_width != MI_DV_WIDTH) return -1;
+  if (fmt->pixelformat == GAVL_YUV_422_P) {
+    if (fmt->image_height == MI_DV_HEIGHT) return MI_DV_SYS_525_60_422;
+    if (fmt->image_height == MI_DV_625_HEIGHT) return MI_DV_SYS_625_50_422;
+    return -1;
+  }
   if (fmt->image_height == MI_DV_HEIGHT) return MI_DV_SYS_525_60;
   if (fmt->image_height == MI_DV_625_HEIGHT && fmt->pixelformat == GAVL_YUV_420_P) return MI_DV_SYS_625_50;
   return -1;
@@ -68,7 +76,8 @@ static int init_dv_hip(bgav_stream_t *s) {
   const int system = dv_system(s->data.video.format);
   if (system < 0) { /* (a caller that skipped .probe) */
     gavl_log(GAVL_LOG_ERROR, LOG_DOMAIN,
-             "Only 525/60 (720x480) and 625/50 4:2:0 (720x576) 25 Mbit/s DV are decoded on the MI355X");
+             "Only 525/60 4:1:1 (720x480) and 625/50 4:2:0 (720x576) 25 Mbit/s DV and 4:2:2 50 Mbit/s DV of both sizes are "
+             "decoded on the MI355X");
     return 0;
   }
   priv = calloc(1, sizeof(*priv));
@@ -85,8 +94,11 @@ static int init_dv_hip(bgav_stream_t *s) {
   if (system == MI_DV_SYS_525_60) {
     s->data.video.format->frame_height = MI_DV_HEIGHT;
     s->data.video.format->pixelformat = GAVL_YUV_411_P; /* lib/dvframe.c:119: the 525/60 profile's pix_fmt */
+  } else if (system == MI_DV_SYS_525_60_422) {
+    s->data.video.format->frame_height = MI_DV_HEIGHT; /* the pixel format stays GAVL_YUV_422_P (lib/dvframe.c:170-211) */
   } else {
-    s->data.video.format->frame_height = MI_DV_625_HEIGHT; /* the pixel format stays GAVL_YUV_420_P (lib/dvframe.c:129-148) */
+    /* the pixel format stays GAVL_YUV_420_P (lib/dvframe.c:129-148) or GAVL_YUV_422_P */
+    s->data.video.format->frame_height = MI_DV_625_HEIGHT;
   }
   gavl_dictionary_set_string(s->m, GAVL_META_FORMAT, "DV");
   return 1;

@@ -1,5 +1,6 @@
-"""ctypes view of include/mi_dv.h (libmi_dv.so, the DV25 decoder: 525/60 4:1:1 and 625/50 4:2:0).  No CPU path: without the library or a
-gfx950 device construction raises MiDvError with the library's own message."""
+"""ctypes view of include/mi_dv.h (libmi_dv.so, the DV decoder: 525/60 4:1:1 and 625/50 4:2:0 at 25 Mbit/s, both line
+systems in 4:2:2 at 50 Mbit/s).  No CPU path: without the library or a gfx950 device construction raises MiDvError with
+the library's own message."""
 import ctypes as C
 import os
 
@@ -9,12 +10,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 FRAME_BYTES, PICTURE_BYTES, W, H, CW = 120000, 720 * 480 * 3 // 2, 720, 480, 180
 SYS_525_60, SYS_625_50 = 0, 1
 FRAME_BYTES_625, PICTURE_BYTES_625, H_625, CW_625, CH_625 = 144000, 720 * 576 + 2 * 360 * 288, 576, 360, 288
+SYS_525_60_422, SYS_625_50_422 = 4, 5  # the 50 Mbit/s systems: VAUX stype 4 | DSF
+FRAME_BYTES_525_422, PICTURE_BYTES_525_422, FRAME_BYTES_625_422, PICTURE_BYTES_625_422, CW_422 = \
+    240000, 720 * 480 * 2, 288000, 720 * 576 * 2, 360
 # per system: frame bytes, picture bytes, (width, height) of the planes Y, Cb, Cr
 GEOMETRY = {SYS_525_60: (FRAME_BYTES, PICTURE_BYTES, ((W, H), (CW, H), (CW, H))),
-            SYS_625_50: (FRAME_BYTES_625, PICTURE_BYTES_625, ((W, H_625), (CW_625, CH_625), (CW_625, CH_625)))}
+            SYS_625_50: (FRAME_BYTES_625, PICTURE_BYTES_625, ((W, H_625), (CW_625, CH_625), (CW_625, CH_625))),
+            SYS_525_60_422: (FRAME_BYTES_525_422, PICTURE_BYTES_525_422, ((W, H), (CW_422, H), (CW_422, H))),
+            SYS_625_50_422: (FRAME_BYTES_625_422, PICTURE_BYTES_625_422, ((W, H_625), (CW_422, H_625), (CW_422, H_625)))}
 EXPORTS = ["mi_dv_device_count", "mi_dv_create", "mi_dv_destroy", "mi_dv_last_error", "mi_dv_dev_alloc", "mi_dv_dev_free",
            "mi_dv_h2d", "mi_dv_d2h", "mi_dv_sync", "mi_dv_decode_batch", "mi_dv_kernel_times", "mi_dv_decode_frame",
-           "mi_dv_copy_tables", "mi_dv_system_of", "mi_dv_decode_batch_sys", "mi_dv_decode_frame_sys", "mi_dv_mb_place"]
+           "mi_dv_copy_tables", "mi_dv_system_of", "mi_dv_decode_batch_sys", "mi_dv_decode_frame_sys", "mi_dv_mb_place",
+           "mi_dv_profile_of"]
 _LIB = None
 u8p = C.POINTER(C.c_uint8)
 
@@ -56,6 +63,7 @@ def load():
     L.mi_dv_copy_tables.argtypes = [vp, C.c_size_t]
     L.mi_dv_copy_tables.restype = C.c_size_t
     L.mi_dv_system_of.argtypes = [u8p, C.c_size_t]
+    L.mi_dv_profile_of.argtypes = [u8p, C.c_size_t]
     L.mi_dv_decode_batch_sys.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.mi_dv_decode_frame_sys.argtypes = [vp, C.c_int, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int)]
     L.mi_dv_mb_place.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2
@@ -80,14 +88,23 @@ def geometry(system):
 
 
 def system_of(frame):
-    """the system a DIF frame announces (SYS_525_60 / SYS_625_50), -1 for other profiles and short frames (host-side)"""
+    """the 25 Mbit/s system a DIF frame announces (SYS_525_60 / SYS_625_50), -1 for other profiles and short frames
+    (host-side)"""
     frame = np.ascontiguousarray(frame, np.uint8)
     return load().mi_dv_system_of(frame.ctypes.data_as(u8p), frame.nbytes)
 
 
+def profile_of(frame):
+    """the same over all four decodable profiles: SYS_525_60, SYS_625_50, SYS_525_60_422 or SYS_625_50_422; -1 for
+    every other profile and for short frames (host-side)"""
+    frame = np.ascontiguousarray(frame, np.uint8)
+    return load().mi_dv_profile_of(frame.ctypes.data_as(u8p), frame.nbytes)
+
+
 def mb_place(system, seq, slot, m):
     """the kernels' placement of macroblock m of segment `slot` of sequence `seq`: (x, y) — 525/60 in 32-pixel columns and
-    8-line rows, 625/50 in 16 x 16 macroblocks (host-side)"""
+    8-line rows, 625/50 in 16 x 16 macroblocks, the 4:2:2 systems in 16-pixel columns and 8-line rows with `seq` counting
+    both channels' sequences (host-side)"""
     x, y = C.c_int(), C.c_int()
     L = load()
     if L.mi_dv_mb_place(system, seq, slot, m, C.byref(x), C.byref(y)) != 0:
@@ -141,7 +158,7 @@ class MiDv:
 
     def decode_frames(self, frames, system=SYS_525_60):
         """host frames (n x the system's frame bytes, uint8) -> host pictures (n x its picture bytes), through the batch
-        path (525/60: 120000 -> 518400; 625/50: 144000 -> 622080)"""
+        path (525/60: 120000 -> 518400; 625/50: 144000 -> 622080; 4:2:2: 240000 -> 691200, 288000 -> 829440)"""
         fb, pb, _ = geometry(system)
         frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, fb)
         n = frames.shape[0]

@@ -1,0 +1,165 @@
+"""The 50 Mbit/s 4:2:2 DV systems without a GPU: the kernels' macroblock placement (mi_dv_mb_place) against the test
+statement (tests/dv422.py); the host-side profile check over all four decodable profiles (mi_dv_profile_of); what the
+statement's encoder writes into the areas that carry no pixels; the statement's own round trip.  PARITY UNPINNED: both
+statements of the 4:2:2 layout are this repository's reading of SMPTE 314M."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import dv422 as P
+import dvlib as D
+from pkg import ROOT
+
+SYSTEMS = [P.SYS_525_60_422, P.SYS_625_50_422]
+
+
+@pytest.fixture(scope="module")
+def dv():
+    return importlib.import_module("gmerlin-avdecoder_amd.dv")
+
+
+def test_the_python_view_states_the_same_geometry(dv):
+    assert (dv.SYS_525_60_422, dv.SYS_625_50_422) == (4, 5)
+    for system in SYSTEMS:
+        g = P.geometry(system)
+        fb, pb, planes = dv.geometry(system)
+        assert (fb, pb) == (g.frame_bytes, g.picture_bytes)
+        assert planes == ((720, g.h), (360, g.h), (360, g.h))
+    assert (P.geometry(4).frame_bytes, P.geometry(4).picture_bytes, P.geometry(4).segments) == (240000, 691200, 540)
+    assert (P.geometry(5).frame_bytes, P.geometry(5).picture_bytes, P.geometry(5).segments) == (288000, 829440, 648)
+
+
+@pytest.mark.parametrize("system", SYSTEMS)
+def test_422_placement_is_a_bijection_and_matches_the_statement(dv, system):
+    g = P.geometry(system)
+    seen = np.zeros((g.h // 8, 45), np.int32)
+    for seq in range(g.frame_seqs):
+        for slot in range(27):
+            for m in range(5):
+                x, y = dv.mb_place(system, seq, slot, m)
+                assert (x, y) == P.mb_place(system, seq, slot, m), (seq, slot, m)
+                seen[y, x] += 1
+    assert (seen == 1).all()
+    P.maps(system)  # asserts that the destination offsets tile the picture exactly once
+
+
+@pytest.mark.parametrize("args", [(4, 20, 0, 0), (5, 24, 0, 0), (4, 0, 27, 0), (5, 0, 27, 0), (4, 0, 0, 5), (5, 0, 0, 5),
+                                  (4, -1, 0, 0), (5, -1, 0, 0), (4, 0, -1, 0), (5, 0, 0, -1), (2, 0, 0, 0), (3, 0, 0, 0),
+                                  (6, 0, 0, 0)])
+def test_422_placement_refuses_what_is_out_of_range(dv, args):
+    with pytest.raises(dv.MiDvError):
+        dv.mb_place(*args)
+
+
+def test_422_placement_takes_the_last_sequence_of_the_second_channel(dv):
+    assert dv.mb_place(4, 19, 26, 4) == P.mb_place(4, 19, 26, 4)
+    assert dv.mb_place(5, 23, 26, 4) == P.mb_place(5, 23, 26, 4)
+
+
+@pytest.fixture(scope="module")
+def dvframe():
+    from test_dvframe_host import Profile  # the struct of include/mi_dvframe.h
+    subprocess.run(["make", "-C", os.path.join(ROOT, "gmerlin-avdecoder_amd", "csrc"),
+                    os.path.join(ROOT, "gmerlin-avdecoder_amd", "lib", "libmi_dvframe.so")], check=True, capture_output=True)
+    lib = C.CDLL(os.path.join(ROOT, "gmerlin-avdecoder_amd", "lib", "libmi_dvframe.so"))
+    lib.mi_dv_profile_at.restype = C.POINTER(Profile)
+    lib.mi_dv_frame_profile.restype = C.POINTER(Profile)
+    lib.mi_dv_frame_profile.argtypes = [C.POINTER(C.c_uint8)]
+    return lib
+
+
+def test_profile_of_every_profile(dv, dvframe):
+    from test_dvframe_host import make_frame
+    rng = np.random.default_rng(5)
+    assert dvframe.mi_dv_num_profiles() == 9
+    for i in range(9):
+        p = dvframe.mi_dv_profile_at(i).contents
+        f = make_frame(p, rng, apt=1 if i == 2 else 0)
+        got = dvframe.mi_dv_frame_profile(f.ctypes.data_as(C.POINTER(C.c_uint8))).contents
+        assert got.frame_size == p.frame_size and got.pix_fmt == p.pix_fmt  # the frame is of profile i
+        want = {0: dv.SYS_525_60, 1: dv.SYS_625_50, 3: dv.SYS_525_60_422, 4: dv.SYS_625_50_422}.get(i, -1)
+        assert dv.profile_of(f) == want, i
+        assert dv.profile_of(f[:p.frame_size - 1]) == -1, i
+        assert dv.profile_of(f[:400]) == -1, i
+        if dv.system_of(f) != -1:
+            assert dv.system_of(f) == dv.profile_of(f), i
+        if i in (3, 4):
+            assert dv.system_of(f) == -1  # mi_dv_system_of knows the 25 Mbit/s systems only
+            assert (p.frame_size, p.height) == (P.geometry(want).frame_bytes, P.geometry(want).h)
+    # every APT value but 0 marks DVCPRO 625/50 4:1:1
+    p = dvframe.mi_dv_profile_at(1).contents
+    for apt in range(1, 8):
+        assert dv.profile_of(make_frame(p, rng, apt=apt)) == -1
+    # a 525/60 4:2:2 frame is long enough at 240,000 bytes, a 625/50 one is not
+    f = make_frame(dvframe.mi_dv_profile_at(4).contents, rng)
+    assert dv.profile_of(f[:240000]) == -1 and dv.profile_of(f) == dv.SYS_625_50_422
+
+
+def _distinct_blocks(g, seed):
+    """every plane: a level per 8 x 8 block (a 2-D gradient plus a random offset), a gentle gradient and noise inside
+    (tests/test_dv625_cpu.py's picture at this system's plane sizes)"""
+    rng = np.random.default_rng(seed)
+    planes = []
+    for w, h in ((P.W, g.h), (P.CW, g.h), (P.CW, g.h)):
+        by, bx = np.mgrid[0:h // 8, 0:w // 8]
+        level = 40 + (3 * bx + 5 * by + rng.integers(0, 170, bx.shape)) % 170
+        px = np.repeat(np.repeat(level, 8, 0), 8, 1)
+        y, x = np.mgrid[0:h, 0:w]
+        px = px + (x % 8) // 3 + (y % 8) // 3 + rng.integers(-3, 4, (h, w))
+        planes.append(np.clip(px, 0, 255).astype(np.uint8).ravel())
+    return np.concatenate(planes)
+
+
+def _block_means(g, pic):
+    out = []
+    for off, w, h in ((0, P.W, g.h), (P.W * g.h, P.CW, g.h), (P.W * g.h + P.CW * g.h, P.CW, g.h)):
+        plane = pic[off:off + w * h].reshape(h // 8, 8, w // 8, 8).astype(np.float64)
+        out.append(plane.mean(axis=(1, 3)))
+    return out
+
+
+@pytest.mark.parametrize("system", SYSTEMS)
+@pytest.mark.parametrize("flags", [0, 1, 2, 3])
+def test_statement_frames_announce_their_system_and_leave_areas_1_and_3_empty(dv, system, flags):
+    g = P.geometry(system)
+    f = P.encode(system, P.synth422(system, flags, 2, 6), flags)
+    assert f.size == g.frame_bytes and dv.profile_of(f) == system and dv.system_of(f) == -1
+    assert f[3] >> 7 == g.dsf and f[80 * 5 + 48 + 3] & 0x1F == 4
+    blocks = f.reshape(g.frame_seqs, 150, 80)
+    for fs in range(g.frame_seqs):
+        assert (blocks[fs, :, 1] >> 3 & 1 == fs // g.seqs).all() and (blocks[fs, :, 1] >> 4 == fs % g.seqs).all()
+        for v in range(135):
+            mb = blocks[fs, 7 + v + v // 15]
+            for a in (D.AREA_OFF[1], D.AREA_OFF[3]):
+                dc = (int(mb[a]) << 1) | (int(mb[a + 1]) >> 7)  # 9 bits, then mode and class, then the first code word
+                assert dc == 0 and int(mb[a + 1]) & 0x0F == 0b0110, (fs, v, a, int(mb[a]), int(mb[a + 1]))
+
+
+@pytest.mark.parametrize("system", SYSTEMS)
+@pytest.mark.parametrize("flags", [0, 1, 2, 3])
+def test_statement_round_trip_keeps_every_block_in_place(system, flags):
+    """DC survives the encoder's rate control: a block or plane put anywhere else (the wrong channel's rows, the right
+    luma block left, the Cb / Cr order, a wrong shuffle) moves a mean by far more than 4"""
+    g = P.geometry(system)
+    pic = _distinct_blocks(g, 10 * system + flags)
+    got = P.decode(system, P.encode(system, pic, flags))
+    worst = 0.0
+    for i, (a, b) in enumerate(zip(_block_means(g, got), _block_means(g, pic))):
+        d = np.abs(a - b)
+        worst = max(worst, float(d.max()))
+        assert d.max() <= 4, (system, flags, i, float(d.max()), np.unravel_index(d.argmax(), d.shape))
+    print(f"system {system} flags {flags}: largest block-mean deviation {worst:.3f}")
+
+
+@pytest.mark.parametrize("system", SYSTEMS)
+def test_statement_decodes_arbitrary_bytes_deterministically(system):
+    g = P.geometry(system)
+    rng = np.random.default_rng(8 + system)
+    f = rng.integers(0, 256, g.frame_bytes, dtype=np.uint8)
+    a, b = P.decode(system, f), P.decode(system, f.copy())
+    assert a.size == g.picture_bytes and a.dtype == np.uint8 and np.array_equal(a, b)
+    assert not np.array_equal(a, P.decode(system, np.zeros(g.frame_bytes, np.uint8)))

@@ -1,14 +1,16 @@
 """Static resource and instruction-class report of the compiled gfx950 kernels.
 
-    python tools/isa_report.py [--kernel k_decode] [--cflags "..."] [--keep DIR] [--json] [--digest] [--src DIR]
+    python tools/isa_report.py [--unit rtjpeg|dv] [--kernel k_decode] [--cflags "..."] [--keep DIR] [--json] [--digest]
+                               [--src DIR] [--bodies FILE]
 
-Compiles csrc/mi_rtjpeg.hip with -save-temps (device assembly) and prints, per kernel, what the
+Compiles csrc/mi_rtjpeg.hip (--unit dv: csrc/mi_dv.hip) with -save-temps (device assembly) and prints, per kernel, what the
 code object's metadata says (VGPR / SGPR count, scalar-register spills, LDS bytes, scratch) and a
 static census of the instruction stream: vector / scalar / LDS / vector-memory instructions and —
 the figure VERDICT r2 asked to track — v_readlane_b32 / v_writelane_b32 (scalar spills are paid in
 those).  Numbers are static (program text), not dynamic counts.  --digest adds a hash of each kernel's instruction
 text (branch labels renumbered, comments dropped), so that two builds can be shown to compile a kernel to the same
-code; --src compiles another checkout's csrc/ (e.g. the parent commit's) with this tool."""
+code; --src compiles another checkout's csrc/ (e.g. the parent commit's) with this tool; --bodies writes that instruction
+text of the selected kernels to a file, so that `diff` can compare two builds line by line."""
 import argparse
 import hashlib
 import json
@@ -23,17 +25,19 @@ CSRC = os.path.join(ROOT, "gmerlin-avdecoder_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
-def device_asm(cflags, keep=None, csrc=CSRC):
+UNITS = {"rtjpeg": ("mi_rtjpeg", ["mi_rtjpeg.hip", "rtj_tables.cpp"]), "dv": ("mi_dv", ["mi_dv.hip", "dv_tables.cpp"])}
+
+
+def device_asm(cflags, keep=None, csrc=CSRC, unit="rtjpeg"):
     d = keep or tempfile.mkdtemp(prefix="mirtj_isa_")
     os.makedirs(d, exist_ok=True)
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
-           "-save-temps"] + cflags + ["-o", os.path.join(d, "lib.so"), os.path.join(csrc, "mi_rtjpeg.hip"),
-                                      os.path.join(csrc, "rtj_tables.cpp")]
+           "-save-temps"] + cflags + ["-o", os.path.join(d, "lib.so")] + [os.path.join(csrc, f) for f in UNITS[unit][1]]
     r = subprocess.run(cmd, cwd=d, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(r.stdout + r.stderr)
     for f in os.listdir(d):
-        if f.startswith("mi_rtjpeg") and f.endswith("gfx950.s"):
+        if f.startswith(UNITS[unit][0] + "-") and f.endswith("gfx950.s"):
             return os.path.join(d, f)
     raise RuntimeError("no device assembly in " + d)
 
@@ -113,9 +117,10 @@ def parse(path):
             elif op.startswith(("global_", "buffer_", "flat_", "scratch_")):
                 c["vmem"] += 1
         body = [re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s*;.*$", "", ln.strip())) for ln in v["lines"]]
-        digest = hashlib.sha1("\n".join(x for x in body if x).encode()).hexdigest()[:16]
+        body = [x for x in body if x]
+        digest = hashlib.sha1("\n".join(body).encode()).hexdigest()[:16]
         m = meta[k]
-        rep[k] = {"digest": digest, "vgpr": int(m.get("vgpr_count", 0)), "sgpr": int(m.get("sgpr_count", 0)),
+        rep[k] = {"digest": digest, "body": body, "vgpr": int(m.get("vgpr_count", 0)), "sgpr": int(m.get("sgpr_count", 0)),
                   "sgpr_spill": int(m.get("sgpr_spill_count", 0)), "vgpr_spill": int(m.get("vgpr_spill_count", 0)),
                   "lds_bytes": int(m.get("group_segment_fixed_size", 0)),
                   "scratch_bytes": int(m.get("private_segment_fixed_size", 0)), "static": c}
@@ -130,15 +135,22 @@ def main():
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--digest", action="store_true", help="print a hash of each kernel's instruction text")
     ap.add_argument("--src", default=CSRC, help="the csrc/ directory to compile")
+    ap.add_argument("--unit", choices=sorted(UNITS), default="rtjpeg", help="which library's kernels")
+    ap.add_argument("--bodies", default=None, help="write the selected kernels' instruction text (as hashed) to this file")
     a = ap.parse_args()
-    rep = parse(device_asm(a.cflags.split(), a.keep, a.src))
+    rep = parse(device_asm(a.cflags.split(), a.keep, a.src, a.unit))
     names = demangle(list(rep))
     out = {}
     for k, v in rep.items():
-        short = re.sub(r"\(.*", "", names[k]).replace("mirtj::", "").replace("void ", "")
+        short = re.sub(r"\(.*", "", names[k]).replace("mirtj::", "").replace("midv::", "").replace("void ", "")
         if a.kernel and a.kernel not in short:
             continue
         out[short] = v
+    bodies = {k: v.pop("body") for k, v in out.items()}
+    if a.bodies:
+        with open(a.bodies, "w") as f:
+            for k in sorted(bodies):
+                f.write(f"==== {k} ({len(bodies[k])} lines)\n" + "\n".join(bodies[k]) + "\n")
     if a.json:
         print(json.dumps(out, indent=1))
         return
