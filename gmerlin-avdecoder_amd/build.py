@@ -109,8 +109,9 @@ EXP_LIB = os.path.join(LIBDIR, "libmi_rtjpeg_exp.so")
 
 def build_experiments(force=False):
     """The same library with -DMIRTJ_EXPERIMENTS: the measurement switches that leave work out or run forms that were
-    measured slower (exp_env() in mi_rtjpeg.hip) exist in this build only.  For tools/ (MI_RTJ_LIB=...), never shipped
-    as the product and not built by __graft_entry__.build()."""
+    measured slower (exp_env() in mi_rtjpeg.hip) exist in this build only.  For tools/ (MI_RTJ_LIB=...) and for
+    tests/test_gpu_launch_shapes.py, which runs the split form under other wave counts and stripe rotations in a child
+    process; never shipped as the product."""
     if not force and os.path.exists(EXP_LIB) and all(os.path.getmtime(f) <= os.path.getmtime(EXP_LIB) for f in _deps()):
         return EXP_LIB
     old = os.environ.get("MI_RTJ_CFLAGS")

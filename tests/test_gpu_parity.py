@@ -1,9 +1,12 @@
 """Parity tests proper: the HIP path, called through the C ABI (libmi_rtjpeg.so), against the CPU
 oracle and the committed golden vectors.  Bit-exact everywhere — this is integer/byte work.
 Run on the GPU box with `pytest -m gpu`."""
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 import pytest
 
+import launch_shapes as LS
 import rtjlib as R
 from pkg import P
 
@@ -31,21 +34,93 @@ def first_diff(a, b):
     return None if d.size == 0 else (int(d[0]), int(a[d[0]]), int(b[d[0]]), int(d.size))
 
 
-def batch_decode(dev, pkts, prefill=None, align=1, check_index=True):
-    """Independent decode of each packet through a plan.  Returns list of plane arrays."""
-    d_stream, po, pl, hdrs = dev.upload_packets(pkts, align=align)
-    sizes = [frame_bytes(int(p[6]) | (int(p[7]) << 8), int(p[8]) | (int(p[9]) << 8)) for p in pkts]
-    oo = np.zeros(len(pkts), np.uint64)
-    cur = 0
+WORKERS = 16  # oracle work runs on a pool of this size at most, whatever the machine has
+
+
+def pmap(fn, items):
+    items = list(items)
+    with ThreadPoolExecutor(max_workers=max(1, min(WORKERS, len(items)))) as ex:
+        return list(ex.map(fn, items))
+
+
+def oracle_digests(pkts):
+    """digest of the oracle's picture of every packet, each decoded on its own into zeros"""
+    def one(p):
+        want = np.zeros(frame_bytes(*packet_size(p)), np.uint8)
+        R.OracleDecoder().decode(p, want)
+        return R.digest(want)
+    return pmap(one, pkts)
+
+
+def device_digests(dev, d_out, fsz, n):
+    """digest of every picture of an output buffer of n pictures of fsz bytes (read back one at a time)"""
+    return pmap(R.digest, [dev.d2h(d_out, fsz, offset=k * fsz) for k in range(n)])
+
+
+def explain_picture(dev, d_out, fsz, k, pkt, cls, form, frames, split):
+    """the assertion message for picture k of a launch, whose digest is not the oracle's"""
+    w, h = packet_size(pkt)
+    got = dev.d2h(d_out, fsz, offset=k * fsz)
+    want = np.zeros(fsz, np.uint8)
+    R.OracleDecoder().decode(pkt, want)
+    d = np.nonzero(got != want)[0]
+    if d.size == 0:
+        return f"class {cls}, form {form}, picture {k}: digest differs, bytes read back again do not"
+    off = int(d[0])
+    return (f"class {cls} ({w}x{h}), form {form}, picture {k} of {frames}: {d.size} bytes differ from the oracle, first at "
+            f"byte {off}: got {int(got[off])} want {int(want[off])}; "
+            + LS.Shapes().describe_byte(w, h, off, "split" if split else "classic", frame=k, frames=frames))
+
+
+def packet_size(p):
+    return int(p[6]) | (int(p[7]) << 8), int(p[8]) | (int(p[9]) << 8)
+
+
+def batch_layout(sizes, guard=0, odd16=False):
+    """out_offset of every picture and the size of the output buffer.  Pictures start at multiples of 256 — with odd16
+    every other one at a multiple of 16 that is not one of 256 (the contract of mi_rtj_plan_create is 16) — and `guard`
+    bytes lie before the first, between any two and behind the last."""
+    oo = np.zeros(len(sizes), np.uint64)
+    cur = guard
     for i, s in enumerate(sizes):
+        cur = (cur + 255) // 256 * 256
+        if odd16 and i % 2:
+            cur += 16 * (1 + (i // 2) % 15)
         oo[i] = cur
-        cur += (s + 255) // 256 * 256
-    d_out = dev.alloc(cur)
-    dev.memset(d_out, 0 if prefill is None else prefill, cur)
+        cur += s + guard
+    return oo, max(cur, 1)
+
+
+def batch_decode(dev, pkts, prefill=None, align=1, check_index=True, guard=0, odd16=False, report=None, launches=1):
+    """Independent decode of each packet through a plan.  Returns list of plane arrays.
+    guard / odd16: see batch_layout(); every byte of the output buffer outside the pictures must come back as it was
+    filled.  launches: decodes queued back to back without a sync in between.  report: a dict that receives what the
+    plan says about the launch (decode_form(), overlapped())."""
+    d_stream, po, pl, hdrs = dev.upload_packets(pkts, align=align)
+    sizes = [frame_bytes(*packet_size(p)) for p in pkts]
+    oo, total = batch_layout(sizes, guard, odd16)
+    fill = 0 if prefill is None else prefill
+    d_out = dev.alloc(total)
+    dev.memset(d_out, fill, total)
     plan = dev.plan(hdrs, po, pl, oo)
-    plan.decode(d_stream, d_out)
+    for _ in range(launches):
+        plan.decode(d_stream, d_out)
     dev.sync()
-    outs = [dev.d2h(d_out, sizes[i], offset=int(oo[i])) for i in range(len(pkts))]
+    if report is not None:
+        report["form"], report["classic_left"], report["parts_listed"] = plan.decode_form()
+        report["overlapped"] = plan.overlapped()
+        report["out_offsets"] = oo.copy()
+    whole = dev.d2h(d_out, total)
+    outs = [whole[int(oo[i]):int(oo[i]) + sizes[i]] for i in range(len(pkts))]
+    at = 0
+    for i in range(len(pkts) + 1):  # the gaps: guards and alignment padding
+        end = int(oo[i]) if i < len(pkts) else total
+        bad = np.nonzero(whole[at:end] != fill)[0]
+        assert bad.size == 0, (f"byte {at + int(bad[0])} of the output buffer, {int(oo[i - 1]) + sizes[i - 1] if i else 0} + "
+                               f"{int(bad[0])} (outside every picture, before picture {i}) was written: "
+                               f"{int(whole[at + bad[0]])} instead of {fill} ({bad.size} bytes of the gap)")
+        if i < len(pkts):
+            at = end + sizes[i]
     if check_index:
         idx = plan.read_index()
         k = 0
@@ -501,10 +576,11 @@ def test_benchmark_size_digests_from_reference(dev, G, row):
         dev.free(p)
 
 
-def test_full_size_batch_properties(dev):
-    """256 distinct 1080p frames (BASELINE config): decode is deterministic (two passes give the
-    same bytes), independent of batch position (frame k decoded alone == inside the batch), and
-    a sample of frames matches the oracle."""
+def test_full_size_batch_properties(dev, monkeypatch):
+    """256 distinct 1080p frames (BASELINE config), in the form the plan's policy chooses and with the split form
+    forced: decode is deterministic (two passes give the same bytes, every picture), EVERY picture is the oracle's
+    (each launch gives its pictures eight different XCD stripes: a sample would see half of them), and a sample of
+    frames is independent of batch position (frame k decoded alone == inside the batch)."""
     w, h, Q, n = 1920, 1088, 255, 256
     fsz = frame_bytes(w, h)
     d_fr = dev.synth(w, h, 0, n, seed=12345, amp=8)
@@ -516,30 +592,44 @@ def test_full_size_batch_properties(dev):
         hdrs[i, 0:4] = np.frombuffer(np.uint32(pl[i]).tobytes(), np.uint8)
     oo = np.arange(n, dtype=np.uint64) * np.uint64(fsz)
     d_out = dev.alloc(fsz * n)
-    plan = dev.plan(hdrs, po, pl, oo)
-    plan.decode(d_st, d_out)
-    dev.sync()
+    host = dev.d2h(d_st, int(po[-1]) + int(pl[-1]))
+    pkts = [host[int(po[k]):int(po[k]) + int(pl[k])] for k in range(n)]
+    want = oracle_digests(pkts)
+    assert len(want) == n
     sample = [0, 1, 127, 255]
-    first = {k: dev.d2h(d_out, fsz, offset=k * fsz) for k in sample}
-    sums1 = [int(dev.d2h(d_out, 4096, offset=k * fsz + 12345).sum()) for k in range(n)]
-    dev.memset(d_out, 0, fsz * n)
-    plan.decode(d_st, d_out)
-    dev.sync()
-    for k in sample:
-        again = dev.d2h(d_out, fsz, offset=k * fsz)
-        assert first_diff(again, first[k]) is None
-        pkt = dev.d2h(d_st, int(pl[k]), offset=int(po[k]))
-        want = np.zeros(fsz, np.uint8)
-        R.OracleDecoder().decode(pkt, want)
-        assert first_diff(again, want) is None, k
-        alone = np.zeros(fsz, np.uint8)
-        dd = P.MiRtj()
-        dd.decode(pkt, alone)
-        dd.close()
-        assert first_diff(alone, want) is None, k
-    sums2 = [int(dev.d2h(d_out, 4096, offset=k * fsz + 12345).sum()) for k in range(n)]
-    assert sums1 == sums2
-    plan.close()
+    monkeypatch.delenv("MI_RTJ_ROTATE", raising=False)
+    for form, split in (("policy", None), ("split", "1")):
+        with monkeypatch.context() as m:
+            m.delenv("MI_RTJ_SPLIT", raising=False)
+            if split is not None:
+                m.setenv("MI_RTJ_SPLIT", split)
+            plan = dev.plan(hdrs, po, pl, oo)
+        dev.memset(d_out, 0, fsz * n)
+        plan.decode(d_st, d_out)
+        dev.sync()
+        first = {k: dev.d2h(d_out, fsz, offset=k * fsz) for k in sample}
+        pass1 = device_digests(dev, d_out, fsz, n)
+        dev.memset(d_out, 0, fsz * n)
+        plan.decode(d_st, d_out)
+        dev.sync()
+        ran = plan.decode_form()[0]
+        assert ran == 0 if split else ran in (0, 1), (form, plan.decode_form())
+        pass2 = device_digests(dev, d_out, fsz, n)
+        assert pass1 == pass2, (form, [k for k in range(n) if pass1[k] != pass2[k]][:8])
+        for k in range(n):
+            assert pass2[k] == want[k], explain_picture(dev, d_out, fsz, k, pkts[k], "1920x1088 x 256", form, n, ran == 0)
+        for k in sample:
+            again = dev.d2h(d_out, fsz, offset=k * fsz)
+            assert first_diff(again, first[k]) is None
+            wantk = np.zeros(fsz, np.uint8)
+            R.OracleDecoder().decode(pkts[k], wantk)
+            assert first_diff(again, wantk) is None, k
+            alone = np.zeros(fsz, np.uint8)
+            dd = P.MiRtj()
+            dd.decode(pkts[k], alone)
+            dd.close()
+            assert first_diff(alone, wantk) is None, k
+        plan.close()
     dev.free(d_st)
     dev.free(d_out)
 
