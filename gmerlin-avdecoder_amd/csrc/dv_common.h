@@ -1,5 +1,6 @@
 // dv_common.h — what the host side and the gfx950 kernels of the DV decoder share: the constant tables and the
-// four systems' frame and picture layouts (25 Mbit/s: 525/60 4:1:1, 625/50 4:2:0; 50 Mbit/s: both in 4:2:2).
+// five systems' frame and picture layouts (25 Mbit/s: 525/60 4:1:1, 625/50 4:2:0, 625/50 4:1:1 "DVCPRO"; 50 Mbit/s: both
+// line systems in 4:2:2).
 #pragma once
 #include <stdint.h>
 
@@ -32,7 +33,7 @@ constexpr int kSegments = 270;  // video segments per frame: 10 DIF sequences of
 #define MIDV_HD inline
 #endif
 
-// ---- the two 25 Mbit/s systems (include/mi_dv.h: MI_DV_SYS_*) ----
+// ---- the 25 Mbit/s systems (include/mi_dv.h: MI_DV_SYS_*; the third, Sys625_411, is below Sys625) ----
 // A DIF sequence is 150 blocks of 80 bytes in both; video block v (0..134) of a sequence is block 7 + v + v / 15, and
 // five consecutive video blocks are one video segment (27 per sequence).  What differs is the number of sequences, the
 // macroblock shuffle and the picture: place() maps macroblock m (0..4) of segment `slot` (0..26) of sequence `seq` to
@@ -43,20 +44,23 @@ constexpr int kSegments = 270;  // video segments per frame: 10 DIF sequences of
 // halves.  x in 32-pixel columns (0..22), y in 8-line rows (0..59); the shuffle the checker states too (dvo_mb_place).
 // The statement is also a macro: k_dv_decode<Sys525> expands it in place.  As a call it is inlined only after the callee
 // was simplified on its own, and the 525/60 kernel then compiles to other (no faster) code than it did before 625/50
-// existed; expanded, its code stays what it was, instruction for instruction.
-#define MIDV_PLACE_525(seq, slot, m, x32, y8)                                                 \
+// existed; expanded, its code stays what it was, instruction for instruction.  MIDV_PLACE_411 is the statement with the
+// number of DIF sequences as the modulus (10 here; 12 for Sys625_411), MIDV_PLACE_525 what the 525/60 kernel expands.
+#define MIDV_PLACE_411(seqs, seq, slot, m, x32, y8)                                           \
   do {                                                                                        \
     const uint32_t off_ = (m) == 0u ? 2u : (m) == 1u ? 6u : (m) == 2u ? 8u : (m) == 3u ? 0u : 4u;       \
     const uint32_t start_ = (m) == 0u ? 9u : (m) == 1u ? 4u : (m) == 2u ? 13u : (m) == 3u ? 0u : 18u;   \
-    const uint32_t i_ = ((seq) + off_) % 10u;                                                 \
+    const uint32_t i_ = ((seq) + off_) % (seqs);                                              \
     const uint32_t k_ = (slot) + ((m) == 1u || (m) == 2u ? 3u : 0u);                          \
     const uint32_t k6_ = k_ / 6u, km_ = k_ - 6u * k6_;                                        \
     const uint32_t serp_ = k6_ & 1u ? 5u - km_ : km_;                                         \
     (x32) = start_ + k6_;                                                                     \
     (y8) = (x32) > 21u ? 2u * serp_ + 6u * i_ : serp_ + 6u * i_;                              \
   } while (0)
+#define MIDV_PLACE_525(seq, slot, m, x32, y8) MIDV_PLACE_411(10u, seq, slot, m, x32, y8)
 struct Sys525 {
   static constexpr int kId = 0, kChans = 1;
+  static constexpr bool k411 = true;  // 32 x 8 macroblocks, 16 x 16 with split chroma blocks in column 22
   static constexpr int kFrameBytes = 120000, kSeqs = 10, kSegments = kSeqs * 27, kPairs = kSegments / 2;
   static constexpr int kW = 720, kH = 480, kCW = 180, kCH = 480, kPicBytes = kW * kH + 2 * kCW * kCH;
   static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x32, uint32_t& y8) {
@@ -70,6 +74,7 @@ struct Sys525 {
 // upwards in odd columns.  x, y in 16-pixel units (0..44, 0..35).
 struct Sys625 {
   static constexpr int kId = 1, kChans = 1;
+  static constexpr bool k411 = false;
   static constexpr int kFrameBytes = 144000, kSeqs = 12, kSegments = kSeqs * 27, kPairs = kSegments / 2;
   static constexpr int kW = 720, kH = 576, kCW = 360, kCH = 288, kPicBytes = kW * kH + 2 * kCW * kCH;
   static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x16, uint32_t& y16) {
@@ -79,6 +84,20 @@ struct Sys625 {
     const uint32_t c = slot / 3u, r = slot - 3u * c;
     x16 = 9u * col + c;
     y16 = 3u * row + (c & 1u ? 2u - r : r);
+  }
+};
+
+// 625/50 4:1:1 ("DVCPRO" 25 Mbit/s PAL: DSF 1, VAUX stype 0, APT != 0; lib/dvframe.c:149-169; SMPTE 314M as this
+// repository reads it: parity unpinned): the 625/50 frame (12 sequences, 144,000 bytes) with the 525/60 picture layout
+// carried on by two sequences: 720 x 576, Cb / Cr 180 x 576.  Macroblocks, the right-edge column and the shuffle are
+// 525/60's with the sequence count as the modulus: x in 32-pixel columns (0..22), y in 8-line rows (0..71).
+struct Sys625_411 {
+  static constexpr int kId = 3, kChans = 1;
+  static constexpr bool k411 = true;
+  static constexpr int kFrameBytes = 144000, kSeqs = 12, kSegments = kSeqs * 27, kPairs = kSegments / 2;
+  static constexpr int kW = 720, kH = 576, kCW = 180, kCH = 576, kPicBytes = kW * kH + 2 * kCW * kCH;
+  static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x32, uint32_t& y8) {
+    MIDV_PLACE_411(12u, seq, slot, m, x32, y8);
   }
 };
 
@@ -92,6 +111,7 @@ struct Sys625 {
 template <int Id, int Seqs>
 struct Sys422 {
   static constexpr int kId = Id, kChans = 2;
+  static constexpr bool k411 = false;
   static constexpr int kSeqs = Seqs, kFrameBytes = kChans * kSeqs * 150 * 80, kSegments = kChans * kSeqs * 27, kPairs = kSegments / 2;
   static constexpr int kW = 720, kH = 48 * kSeqs, kCW = 360, kCH = kH, kPicBytes = kW * kH + 2 * kCW * kCH;
   static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x16, uint32_t& y8) {
@@ -109,6 +129,10 @@ using Sys625_422 = Sys422<5, 12>;  // 288,000-byte frames, 720 x 576
 static_assert(Sys525::kFrameBytes == Sys525::kSeqs * 150 * 80 && Sys625::kFrameBytes == Sys625::kSeqs * 150 * 80, "DIF frames");
 static_assert(Sys525::kPicBytes == kPicBytes && Sys525::kFrameBytes == kFrameBytes && Sys525::kSegments == kSegments, "525/60");
 static_assert(Sys625::kPicBytes == 622080 && Sys625::kPairs * 2 == Sys625::kSegments, "625/50");
+static_assert(Sys625_411::kFrameBytes == Sys625_411::kSeqs * 150 * 80 && Sys625_411::kFrameBytes == Sys625::kFrameBytes &&
+                  Sys625_411::kSegments == 324 && Sys625_411::kPairs == 162 && Sys625_411::kPairs * 2 == Sys625_411::kSegments &&
+                  Sys625_411::kPicBytes == 622080 && Sys625_411::kCW * 4 == Sys625_411::kW && Sys625_411::kCH == Sys625_411::kH,
+              "625/50 4:1:1");
 static_assert(Sys525_422::kFrameBytes == 240000 && Sys525_422::kH == 480 && Sys525_422::kPicBytes == 691200 &&
                   Sys525_422::kSegments == 540 && Sys525_422::kPairs == 270, "525/60 4:2:2");
 static_assert(Sys625_422::kFrameBytes == 288000 && Sys625_422::kH == 576 && Sys625_422::kPicBytes == 829440 &&

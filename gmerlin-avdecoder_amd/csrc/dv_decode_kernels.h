@@ -1,8 +1,9 @@
-// dv_decode_kernels.h — gfx950 kernel of the DV video decoder: 525/60 4:1:1 and 625/50 4:2:0 at 25 Mbit/s, both line
-// systems in 4:2:2 at 50 Mbit/s (the arithmetic: DESIGN.md section 9; the format: IEC 61834-2 / SMPTE 314M; nothing in
-// the reference to follow — lib/dvframe.c:663-676 passes the DIF frame on).
+// dv_decode_kernels.h — gfx950 kernel of the DV video decoder: 525/60 4:1:1, 625/50 4:2:0 and 625/50 4:1:1 at 25 Mbit/s,
+// both line systems in 4:2:2 at 50 Mbit/s (the arithmetic: DESIGN.md section 9; the format: IEC 61834-2 / SMPTE 314M;
+// nothing in the reference to follow — lib/dvframe.c:663-676 passes the DIF frame on).
 //
-//   k_dv_decode<Sys>  one instantiation per system (dv_common.h: Sys525, Sys625, Sys525_422, Sys625_422), which differ
+//   k_dv_decode<Sys>  one instantiation per system (dv_common.h: Sys525, Sys625, Sys625_411, Sys525_422, Sys625_422),
+//                  which differ
 //                  only in the frame's sequence count, the macroblock shuffle, where a block's pixels go and, for the
 //                  4:2:2 systems, in which areas carry pixels at all (areas 1 and 3 are parsed and dropped).
 //                  One wave per two video segments (2 x 5 compressed macroblocks = 60 blocks, one lane each):
@@ -387,13 +388,17 @@ __global__ __launch_bounds__(64 * kDvWaves) void k_dv_decode(const uint8_t* __re
   uint32_t mx, my8;
   if constexpr (Sys::kId == Sys525::kId)
     MIDV_PLACE_525(seq, slot, mbi, mx, my8);  // (Sys525::place, expanded: dv_common.h)
+  else if constexpr (Sys::k411)
+    MIDV_PLACE_411((uint32_t)Sys::kSeqs, seq, slot, mbi, mx, my8);  // (Sys625_411::place, expanded like it)
   else
     Sys::place(seq, slot, mbi, mx, my8);
   uint8_t* pic = pics + (size_t)blockIdx.y * Sys::kPicBytes;
   typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
   uint32_t stride, org;
   bool halves = false;
-  if constexpr (Sys::kId == Sys525::kId) {  // mx: 32-pixel column, my8: 8-line row
+  if constexpr (Sys::k411) {  // 525/60 and 625/50 4:1:1: mx: 32-pixel column, my8: 8-line row
+    constexpr uint32_t kW = Sys::kW, kH = Sys::kH, kCW = Sys::kCW;  // (the chroma planes are as high as the picture)
+    static_assert(Sys::kCH == Sys::kH, "4:1:1");
     const uint32_t x32 = mx, y8 = my8;
     const bool edge = x32 == 22u;
     if (j < 4u) {

@@ -1,5 +1,5 @@
-// mi_dv.hip — C ABI (include/mi_dv.h) of the MI355X DV decoder (25 Mbit/s: 525/60 4:1:1, 625/50 4:2:0; 50 Mbit/s: both
-// line systems in 4:2:2).  No CPU path: without a gfx950 device every call fails with a message.
+// mi_dv.hip — C ABI (include/mi_dv.h) of the MI355X DV decoder (25 Mbit/s: 525/60 4:1:1, 625/50 4:2:0, 625/50 4:1:1;
+// 50 Mbit/s: both line systems in 4:2:2).  No CPU path: without a gfx950 device every call fails with a message.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -29,6 +29,10 @@ static_assert(MI_DV_SYS_525_60_422 == Sys525_422::kId && MI_DV_525_422_FRAME_BYT
                   Sys525_422::kCH == Sys525_422::kH && Sys625_422::kCH == Sys625_422::kH && MI_DV_WIDTH == Sys525_422::kW &&
                   MI_DV_WIDTH == Sys625_422::kW,
               "header and kernels agree (4:2:2)");
+static_assert(MI_DV_SYS_625_50_411 == Sys625_411::kId && MI_DV_625_FRAME_BYTES == Sys625_411::kFrameBytes &&
+                  MI_DV_625_411_PICTURE_BYTES == Sys625_411::kPicBytes && MI_DV_625_411_CHROMA_WIDTH == Sys625_411::kCW &&
+                  MI_DV_625_HEIGHT == Sys625_411::kH && MI_DV_625_HEIGHT == Sys625_411::kCH && MI_DV_WIDTH == Sys625_411::kW,
+              "header and kernels agree (625/50 4:1:1)");
 static_assert(MI_DV_SYS_525_60_422 == (0x4 | 0) && MI_DV_SYS_625_50_422 == (0x4 | 1), "4:2:2 system = stype | DSF");
 
 namespace {
@@ -266,6 +270,7 @@ int mi_dv_decode_batch(mi_dv_ctx* c, const void* d_frames, int n, void* d_pics) 
 int mi_dv_decode_batch_sys(mi_dv_ctx* c, int system, const void* d_frames, int n, void* d_pics) {
   if (system == MI_DV_SYS_525_60) return launch<Sys525>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
   if (system == MI_DV_SYS_625_50) return launch<Sys625>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
+  if (system == MI_DV_SYS_625_50_411) return launch<Sys625_411>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
   if (system == MI_DV_SYS_525_60_422) return launch<Sys525_422>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
   if (system == MI_DV_SYS_625_50_422) return launch<Sys625_422>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
   return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_batch_sys: unknown system %d", system);
@@ -325,10 +330,19 @@ int mi_dv_profile_of(const uint8_t* frame, size_t len) {
   return mi_dv_system_of(frame, len);
 }
 
+int mi_dv_kind_of(const uint8_t* frame, size_t len) {
+  // lib/dvframe.c:303: DSF 1 with stype 0 is the IEC 4:2:0 profile for APT 0 and DVCPRO 625/50 4:1:1 for any other APT
+  if (!frame || len < 80 * 6) return -1;
+  const int dsf = frame[3] >> 7, apt = frame[5] & 7, stype = frame[80 * 5 + 48 + 3] & 0x1f;
+  if (dsf == 1 && stype == 0 && apt != 0) return len >= (size_t)Sys625_411::kFrameBytes ? MI_DV_SYS_625_50_411 : -1;
+  return mi_dv_profile_of(frame, len);
+}
+
 int mi_dv_decode_frame_sys(mi_dv_ctx* c, int system, const uint8_t* frame, size_t len, uint8_t* const planes[3],
                            const int strides[3]) {
   if (system == MI_DV_SYS_525_60) return mi_dv_decode_frame(c, frame, len, planes, strides);
-  if (system != MI_DV_SYS_625_50 && system != MI_DV_SYS_525_60_422 && system != MI_DV_SYS_625_50_422)
+  if (system != MI_DV_SYS_625_50 && system != MI_DV_SYS_625_50_411 && system != MI_DV_SYS_525_60_422 &&
+      system != MI_DV_SYS_625_50_422)
     return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame_sys: unknown system %d", system);
   if (!c || !frame || !planes || !strides || !planes[0] || !planes[1] || !planes[2])
     return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame_sys: NULL argument");
@@ -338,6 +352,15 @@ int mi_dv_decode_frame_sys(mi_dv_ctx* c, int system, const uint8_t* frame, size_
     if (mi_dv_system_of(frame, len) != MI_DV_SYS_625_50)
       return fail(c, MI_DV_ERR_FORMAT, "not a 625/50 25 Mbit/s 4:2:0 DV frame (DSF %d, APT %d, stype 0x%02x)", frame[3] >> 7,
                   frame[5] & 7, frame[80 * 5 + 48 + 3] & 0x1f);
+    return decode_one<S>(c, "mi_dv_decode_frame_sys", frame, planes, strides);
+  }
+  if (system == MI_DV_SYS_625_50_411) {
+    using S = Sys625_411;
+    if (len < (size_t)S::kFrameBytes)
+      return fail(c, MI_DV_ERR_FORMAT, "DIF frame of %zu bytes: 625/50 4:1:1 frames have %d", len, S::kFrameBytes);
+    if (mi_dv_kind_of(frame, len) != MI_DV_SYS_625_50_411)
+      return fail(c, MI_DV_ERR_FORMAT, "not a 625/50 25 Mbit/s 4:1:1 (DVCPRO) DV frame (DSF %d, APT %d, stype 0x%02x; expected DSF 1, "
+                  "APT not 0, stype 0x00)", frame[3] >> 7, frame[5] & 7, frame[80 * 5 + 48 + 3] & 0x1f);
     return decode_one<S>(c, "mi_dv_decode_frame_sys", frame, planes, strides);
   }
   // the 50 Mbit/s systems: DSF = byte 3 bit 7, stype = byte 80*5+48+3 & 0x1f must be 0x4 (lib/dvframe.c:298-316)
@@ -356,6 +379,7 @@ int mi_dv_decode_frame_sys(mi_dv_ctx* c, int system, const uint8_t* frame, size_
 int mi_dv_mb_place(int system, int seq, int slot, int m, int* x, int* y) {
   const int seqs = system == MI_DV_SYS_525_60       ? Sys525::kSeqs
                    : system == MI_DV_SYS_625_50     ? Sys625::kSeqs
+                   : system == MI_DV_SYS_625_50_411 ? Sys625_411::kSeqs
                    : system == MI_DV_SYS_525_60_422 ? 2 * Sys525_422::kSeqs  // (both channels' sequences, in byte order)
                    : system == MI_DV_SYS_625_50_422 ? 2 * Sys625_422::kSeqs
                                                     : 0;
@@ -364,6 +388,7 @@ int mi_dv_mb_place(int system, int seq, int slot, int m, int* x, int* y) {
   uint32_t ux, uy;
   if (system == MI_DV_SYS_525_60) Sys525::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
   else if (system == MI_DV_SYS_625_50) Sys625::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
+  else if (system == MI_DV_SYS_625_50_411) Sys625_411::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
   else if (system == MI_DV_SYS_525_60_422) Sys525_422::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
   else Sys625_422::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
   *x = (int)ux;

@@ -1,6 +1,7 @@
 /*
- * video_dv_mi355x.c — a bgav_video_decoder_t for DV video on an MI355X: at 25 Mbit/s 525/60 (NTSC, 4:1:1) and 625/50
- * (PAL) in the IEC 4:2:0 profile, at 50 Mbit/s (DVCPRO50) both line systems in 4:2:2.
+ * video_dv_mi355x.c — a bgav_video_decoder_t for DV video on an MI355X: at 25 Mbit/s 525/60 (NTSC, 4:1:1), 625/50
+ * (PAL) in the IEC 4:2:0 profile and, opted in with MI_DV_625_411=1, 625/50 in the DVCPRO 4:1:1 profile; at 50 Mbit/s
+ * (DVCPRO50) both line systems in 4:2:2.
  *
  * In gmerlin-avdecoder DV pixels are libavcodec's: lib/dvframe.c:663-676 hands each 120,000-byte DIF frame on as a
  * video packet, and the "FFmpeg DV decoder" entry of lib/video_ffmpeg.c:1572-1575 decodes it for the fourccs of
@@ -9,9 +10,11 @@
  * stream is 720 x 480, or 720 x 576 with the pixel format GAVL_YUV_420_P or GAVL_YUV_422_P.  The demultiplexer sets
  * the pixel format from the DIF profile (lib/dvframe.c:490-500; lib/parse_dv.c:51 for DV in other containers): a stream
  * of either height with GAVL_YUV_422_P is DVCPRO50 and decodes to 4:2:2 pictures; a 720 x 480 stream with any other or no
- * pixel format is 525/60 4:1:1; a 625/50 stream at 25 Mbit/s is ours only in the IEC 4:2:0 profile.  Every other DV
- * flavour (DVCPRO 625/50 4:1:1, a 720 x 576 stream whose pixel format is not known, DVCPRO HD) and every host without
- * the device still go to the FFmpeg decoder.  The pixels come from include/mi_dv.h: mi_dv_decode_frame_sys with the
+ * pixel format is 525/60 4:1:1; a 625/50 stream at 25 Mbit/s is ours in the IEC 4:2:0 profile and, only where the process
+ * environment holds MI_DV_625_411=1, in the DVCPRO 4:1:1 profile (720 x 576 with GAVL_YUV_411_P, lib/dvframe.c:149-169):
+ * that layout is the least certain of this decoder's (include/mi_dv.h: parity unpinned), so it is opt-in until it is
+ * pinned.  Unset, or set to anything else, such a stream is declined as before.  Every other DV flavour (a 720 x 576
+ * stream whose pixel format is not known, DVCPRO HD) and every host without the device still go to the FFmpeg decoder.  The pixels come from include/mi_dv.h: mi_dv_decode_frame_sys with the
  * system the stream was opened with.
  *
  * Integration: add this file to lib/Makefile.am, declare
@@ -50,8 +53,15 @@ static const uint32_t dv_fourccs[] = {
 #define DV_FOURCCS bgav_dv_fourccs /* include/avdec_private.h:1435 */
 #endif
 
+/* MI_DV_625_411=1 in the process environment: 720 x 576 GAVL_YUV_411_P streams are taken too (read where it is needed, so
+ * that .probe and .init of one process agree) */
+static int dv_625_411_opted_in(void) {
+  const char *e = getenv("MI_DV_625_411");
+  return e && !strcmp(e, "1");
+}
+
 /* the system of a stream by its format: GAVL_YUV_422_P is the 50 Mbit/s system of the stream's height; otherwise
- * 720 x 480 is 525/60 4:1:1 and 720 x 576 is 625/50 only in the 4:2:0 profile; -1 else */
+ * 720 x 480 is 525/60 4:1:1 and 720 x 576 is 625/50 in the 4:2:0 profile, or in the 4:1:1 profile when opted in; -1 else */
 static int dv_system(const gavl_video_format_t *fmt) {
   if (!fmt || fmt->image_width != MI_DV_WIDTH) return -1;
   if (fmt->pixelformat == GAVL_YUV_422_P) {
@@ -61,6 +71,8 @@ static int dv_system(const gavl_video_format_t *fmt) {
   }
   if (fmt->image_height == MI_DV_HEIGHT) return MI_DV_SYS_525_60;
   if (fmt->image_height == MI_DV_625_HEIGHT && fmt->pixelformat == GAVL_YUV_420_P) return MI_DV_SYS_625_50;
+  if (fmt->image_height == MI_DV_625_HEIGHT && fmt->pixelformat == GAVL_YUV_411_P && dv_625_411_opted_in())
+    return MI_DV_SYS_625_50_411;
   return -1;
 }
 
@@ -76,8 +88,8 @@ static int init_dv_hip(bgav_stream_t *s) {
   const int system = dv_system(s->data.video.format);
   if (system < 0) { /* (a caller that skipped .probe) */
     gavl_log(GAVL_LOG_ERROR, LOG_DOMAIN,
-             "Only 525/60 4:1:1 (720x480) and 625/50 4:2:0 (720x576) 25 Mbit/s DV and 4:2:2 50 Mbit/s DV of both sizes are "
-             "decoded on the MI355X");
+             "Only 525/60 4:1:1 (720x480) and 625/50 4:2:0 (720x576) 25 Mbit/s DV, 625/50 4:1:1 (720x576) with MI_DV_625_411=1 "
+             "and 4:2:2 50 Mbit/s DV of both sizes are decoded on the MI355X");
     return 0;
   }
   priv = calloc(1, sizeof(*priv));
@@ -97,7 +109,7 @@ static int init_dv_hip(bgav_stream_t *s) {
   } else if (system == MI_DV_SYS_525_60_422) {
     s->data.video.format->frame_height = MI_DV_HEIGHT; /* the pixel format stays GAVL_YUV_422_P (lib/dvframe.c:170-211) */
   } else {
-    /* the pixel format stays GAVL_YUV_420_P (lib/dvframe.c:129-148) or GAVL_YUV_422_P */
+    /* the pixel format stays GAVL_YUV_420_P (lib/dvframe.c:129-148), GAVL_YUV_411_P (:149-169) or GAVL_YUV_422_P */
     s->data.video.format->frame_height = MI_DV_625_HEIGHT;
   }
   gavl_dictionary_set_string(s->m, GAVL_META_FORMAT, "DV");

@@ -1,5 +1,5 @@
-"""ctypes view of include/mi_dv.h (libmi_dv.so, the DV decoder: 525/60 4:1:1 and 625/50 4:2:0 at 25 Mbit/s, both line
-systems in 4:2:2 at 50 Mbit/s).  No CPU path: without the library or a gfx950 device construction raises MiDvError with
+"""ctypes view of include/mi_dv.h (libmi_dv.so, the DV decoder: 525/60 4:1:1, 625/50 4:2:0 and 625/50 4:1:1 at
+25 Mbit/s, both line systems in 4:2:2 at 50 Mbit/s).  No CPU path: without the library or a gfx950 device construction raises MiDvError with
 the library's own message."""
 import ctypes as C
 import os
@@ -13,15 +13,18 @@ FRAME_BYTES_625, PICTURE_BYTES_625, H_625, CW_625, CH_625 = 144000, 720 * 576 + 
 SYS_525_60_422, SYS_625_50_422 = 4, 5  # the 50 Mbit/s systems: VAUX stype 4 | DSF
 FRAME_BYTES_525_422, PICTURE_BYTES_525_422, FRAME_BYTES_625_422, PICTURE_BYTES_625_422, CW_422 = \
     240000, 720 * 480 * 2, 288000, 720 * 576 * 2, 360
+SYS_625_50_411 = 3  # DVCPRO 625/50 4:1:1 (DSF 1, stype 0, APT != 0): 625/50 frames, Y 720 x 576, Cb / Cr 180 x 576
+CW_625_411, PICTURE_BYTES_625_411 = 180, 720 * 576 + 2 * 180 * 576
 # per system: frame bytes, picture bytes, (width, height) of the planes Y, Cb, Cr
 GEOMETRY = {SYS_525_60: (FRAME_BYTES, PICTURE_BYTES, ((W, H), (CW, H), (CW, H))),
             SYS_625_50: (FRAME_BYTES_625, PICTURE_BYTES_625, ((W, H_625), (CW_625, CH_625), (CW_625, CH_625))),
+            SYS_625_50_411: (FRAME_BYTES_625, PICTURE_BYTES_625_411, ((W, H_625), (CW_625_411, H_625), (CW_625_411, H_625))),
             SYS_525_60_422: (FRAME_BYTES_525_422, PICTURE_BYTES_525_422, ((W, H), (CW_422, H), (CW_422, H))),
             SYS_625_50_422: (FRAME_BYTES_625_422, PICTURE_BYTES_625_422, ((W, H_625), (CW_422, H_625), (CW_422, H_625)))}
 EXPORTS = ["mi_dv_device_count", "mi_dv_create", "mi_dv_destroy", "mi_dv_last_error", "mi_dv_dev_alloc", "mi_dv_dev_free",
            "mi_dv_h2d", "mi_dv_d2h", "mi_dv_sync", "mi_dv_decode_batch", "mi_dv_kernel_times", "mi_dv_decode_frame",
            "mi_dv_copy_tables", "mi_dv_system_of", "mi_dv_decode_batch_sys", "mi_dv_decode_frame_sys", "mi_dv_mb_place",
-           "mi_dv_profile_of"]
+           "mi_dv_profile_of", "mi_dv_kind_of"]
 _LIB = None
 u8p = C.POINTER(C.c_uint8)
 
@@ -64,6 +67,7 @@ def load():
     L.mi_dv_copy_tables.restype = C.c_size_t
     L.mi_dv_system_of.argtypes = [u8p, C.c_size_t]
     L.mi_dv_profile_of.argtypes = [u8p, C.c_size_t]
+    L.mi_dv_kind_of.argtypes = [u8p, C.c_size_t]
     L.mi_dv_decode_batch_sys.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.mi_dv_decode_frame_sys.argtypes = [vp, C.c_int, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int)]
     L.mi_dv_mb_place.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2
@@ -101,15 +105,30 @@ def profile_of(frame):
     return load().mi_dv_profile_of(frame.ctypes.data_as(u8p), frame.nbytes)
 
 
-def mb_place(system, seq, slot, m):
-    """the kernels' placement of macroblock m of segment `slot` of sequence `seq`: (x, y) — 525/60 in 32-pixel columns and
-    8-line rows, 625/50 in 16 x 16 macroblocks, the 4:2:2 systems in 16-pixel columns and 8-line rows with `seq` counting
-    both channels' sequences (host-side)"""
+def kind_of(frame):
+    """the same over all five decodable profiles: those of profile_of and SYS_625_50_411 (DSF 1, stype 0, APT != 0), for
+    which profile_of and system_of keep answering -1; -1 for every other profile and for short frames (host-side)"""
+    frame = np.ascontiguousarray(frame, np.uint8)
+    return load().mi_dv_kind_of(frame.ctypes.data_as(u8p), frame.nbytes)
+
+
+def place_of(system, seq, slot, m):
+    """the kernels' placement of macroblock m of segment `slot` of sequence `seq` for any of the five systems: (x, y) —
+    525/60 and 625/50 4:1:1 in 32-pixel columns and 8-line rows (0..59 / 0..71), 625/50 in 16 x 16 macroblocks, the 4:2:2
+    systems in 16-pixel columns and 8-line rows with `seq` counting both channels' sequences (host-side)"""
     x, y = C.c_int(), C.c_int()
     L = load()
     if L.mi_dv_mb_place(system, seq, slot, m, C.byref(x), C.byref(y)) != 0:
         raise MiDvError(L.mi_dv_last_error(None).decode())
     return x.value, y.value
+
+
+def mb_place(system, seq, slot, m):
+    """place_of for the four systems profile_of names.  To this function 3 stays no system, as to profile_of and system_of
+    (tests/test_dv422_cpu.py holds it to that): SYS_625_50_411 goes through place_of, as its frames go through kind_of"""
+    if system == SYS_625_50_411:
+        raise MiDvError(f"mb_place: system {system} is place_of's (as kind_of is to profile_of)")
+    return place_of(system, seq, slot, m)
 
 
 class MiDv:
@@ -158,7 +177,7 @@ class MiDv:
 
     def decode_frames(self, frames, system=SYS_525_60):
         """host frames (n x the system's frame bytes, uint8) -> host pictures (n x its picture bytes), through the batch
-        path (525/60: 120000 -> 518400; 625/50: 144000 -> 622080; 4:2:2: 240000 -> 691200, 288000 -> 829440)"""
+        path (525/60: 120000 -> 518400; 625/50, 4:2:0 and 4:1:1: 144000 -> 622080; 4:2:2: 240000 -> 691200, 288000 -> 829440)"""
         fb, pb, _ = geometry(system)
         frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, fb)
         n = frames.shape[0]

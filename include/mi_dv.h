@@ -1,7 +1,8 @@
 /*
- * mi_dv.h — C ABI of the MI355X (gfx950) DV video decoder.  Four systems.  At 25 Mbit/s: 525/60 (NTSC), 120,000-byte
- * DIF frames in, 720 x 480 4:1:1 pictures out; and 625/50 (PAL) in the IEC 4:2:0 profile, 144,000-byte DIF frames in,
- * 720 x 576 4:2:0 pictures out.  At 50 Mbit/s ("DVCPRO50", two DIF channels): 525/60, 240,000-byte frames in, 720 x 480
+ * mi_dv.h — C ABI of the MI355X (gfx950) DV video decoder.  Five systems.  At 25 Mbit/s: 525/60 (NTSC), 120,000-byte
+ * DIF frames in, 720 x 480 4:1:1 pictures out; 625/50 (PAL) in the IEC 4:2:0 profile, 144,000-byte DIF frames in,
+ * 720 x 576 4:2:0 pictures out; and 625/50 in the DVCPRO 4:1:1 profile, 144,000-byte DIF frames in, 720 x 576 4:1:1
+ * pictures out.  At 50 Mbit/s ("DVCPRO50", two DIF channels): 525/60, 240,000-byte frames in, 720 x 480
  * 4:2:2 pictures out; and 625/50, 288,000-byte frames in, 720 x 576 4:2:2 pictures out.  Plain C types only; libmi_dv.so.
  *
  * Where it sits in gmerlin-avdecoder.  lib/dvframe.c:663-676 (bgav_dv_dec_get_video_packet) hands every DIF frame on
@@ -11,8 +12,10 @@
  * registered for those fourccs in front of the FFmpeg one calls mi_dv_decode_frame with
  * gavl_packet_t::buf and the planes / strides of the gavl_video_frame_t (GAVL_YUV_411_P: Y, Cb, Cr).  For the 625/50
  * 4:2:0 profile (lib/dvframe.c:129-148, GAVL_YUV_420_P) it calls mi_dv_decode_frame_sys with MI_DV_SYS_625_50, for the
- * two DVCPRO50 profiles (lib/dvframe.c:170-211, GAVL_YUV_422_P) with MI_DV_SYS_525_60_422 / MI_DV_SYS_625_50_422.  The
- * other profiles of lib/dvframe.c:106-296 (DVCPRO 625/50 4:1:1, DVCPRO HD) are not decoded here.
+ * two DVCPRO50 profiles (lib/dvframe.c:170-211, GAVL_YUV_422_P) with MI_DV_SYS_525_60_422 / MI_DV_SYS_625_50_422, for
+ * the DVCPRO 625/50 4:1:1 profile (lib/dvframe.c:149-169, GAVL_YUV_411_P) with MI_DV_SYS_625_50_411 — the plugin takes
+ * such streams only when the process environment holds MI_DV_625_411=1.  These are all the
+ * standard-definition profiles of lib/dvframe.c:106-296; the DVCPRO HD ones are not decoded here.
  *
  * PARITY UNPINNED: the reference holds no DV pixel decoder to compare with and none is reachable from the build
  * container.  The arithmetic is stated in oracle/dv_oracle.c (written from the published format, from memory); the
@@ -22,7 +25,9 @@
  * tests/dv625.py, moves whole video segments between 625/50 and 525/60 frames around the unchanged oracle.  The 4:2:2
  * layout (two channels back to back, areas 1 and 3 of the compressed macroblock without pixels, 16 x 8 macroblocks, the
  * super-block row 2 row + channel: DESIGN.md section 9.3) is this repository's reading of SMPTE 314M, unpinned in the
- * same way; its checker is tests/dv422.py.
+ * same way; its checker is tests/dv422.py.  The 625/50 4:1:1 layout (the 625/50 frame, the 525/60 macroblocks, right-edge
+ * column and shuffle with 12 sequences as the modulus: DESIGN.md section 9.4) is a reading of SMPTE 314M from memory and
+ * the least certain of all, unpinned in the same way; its checker is tests/dv411p.py.
  */
 #ifndef MI_DV_H
 #define MI_DV_H
@@ -37,8 +42,12 @@ enum { MI_DV_FRAME_BYTES = 120000, MI_DV_WIDTH = 720, MI_DV_HEIGHT = 480, MI_DV_
        MI_DV_PICTURE_BYTES = 720 * 480 * 3 / 2 };
 /* the systems (the DSF bit of the DIF header), and the 625/50 geometry: Y 720 x 576, Cb 360 x 288, Cr 360 x 288 */
 enum { MI_DV_SYS_525_60 = 0, MI_DV_SYS_625_50 = 1 };
-/* the 50 Mbit/s 4:2:2 systems (VAUX stype 0x4 | DSF; 2 and 3 are no systems): Y 720 x 480 / 576, Cb and Cr 360 wide and
- * as high as the picture */
+/* 625/50 in the DVCPRO 4:1:1 profile (DSF 1, VAUX stype 0, APT != 0): MI_DV_625_FRAME_BYTES in, Y 720 x 576, Cb 180 x 576,
+ * Cr 180 x 576 out.  (2 is no system.) */
+enum { MI_DV_SYS_625_50_411 = 3 };
+enum { MI_DV_625_411_CHROMA_WIDTH = 180, MI_DV_625_411_PICTURE_BYTES = 720 * 576 + 2 * 180 * 576 };
+/* the 50 Mbit/s 4:2:2 systems (VAUX stype 0x4 | DSF; 2 is no system, 3 is the one above): Y 720 x 480 / 576, Cb and Cr 360
+ * wide and as high as the picture */
 enum { MI_DV_SYS_525_60_422 = 4, MI_DV_SYS_625_50_422 = 5 };
 enum { MI_DV_525_422_FRAME_BYTES = 240000, MI_DV_525_422_PICTURE_BYTES = 720 * 480 * 2, MI_DV_625_422_FRAME_BYTES = 288000,
        MI_DV_625_422_PICTURE_BYTES = 720 * 576 * 2, MI_DV_422_CHROMA_WIDTH = 360 };
@@ -84,26 +93,34 @@ size_t mi_dv_copy_tables(void *out, size_t cap);
 /* The 25 Mbit/s system a DIF frame of `len` bytes belongs to, from its header (lib/dvframe.c:298-316): MI_DV_SYS_525_60
  * for DSF 0 with VAUX stype 0, MI_DV_SYS_625_50 for DSF 1 with stype 0 and APT 0; -1 for anything else (DVCPRO 625/50
  * 4:1:1, which is DSF 1 with APT != 0; DVCPRO50; the HD profiles) and for a frame shorter than its system's.  It knows
- * the 25 Mbit/s systems only: mi_dv_profile_of answers for all four.  Host only. */
+ * the two 25 Mbit/s systems it names only: mi_dv_profile_of adds the 4:2:2 ones, mi_dv_kind_of answers for all five.
+ * Host only. */
 int mi_dv_system_of(const uint8_t *frame, size_t len);
 /* The same for every profile this library decodes: 0, 1, 4 or 5 (MI_DV_SYS_*; stype 0x4 is DVCPRO50, whose system is
  * stype | DSF); -1 for anything else and for a frame shorter than its system's.  Equal to mi_dv_system_of wherever that
  * is not -1.  Host only. */
 int mi_dv_profile_of(const uint8_t *frame, size_t len);
+/* The same for every profile this library decodes: 0, 1, 3, 4 or 5.  3 (MI_DV_SYS_625_50_411) is DSF 1 with stype 0, APT
+ * != 0 and at least MI_DV_625_FRAME_BYTES; -1 for anything else and for a frame shorter than its system's.  Equal to
+ * mi_dv_profile_of wherever that is not -1 (which keeps answering -1 for DVCPRO 625/50 4:1:1, as mi_dv_system_of
+ * does).  Host only. */
+int mi_dv_kind_of(const uint8_t *frame, size_t len);
 /* mi_dv_decode_batch for any system: frames of the system's size in, pictures of the system's size out
  * (MI_DV_625_FRAME_BYTES / MI_DV_625_PICTURE_BYTES for 625/50: Y 720 x 576, Cb 360 x 288, Cr 360 x 288, tightly
- * packed; MI_DV_525_422_* / MI_DV_625_422_* for the 4:2:2 systems: Y 720 x H, Cb 360 x H, Cr 360 x H).  The same rules
+ * packed; MI_DV_625_FRAME_BYTES / MI_DV_625_411_PICTURE_BYTES for 625/50 4:1:1: Y 720 x 576, Cb 180 x 576, Cr 180 x 576;
+ * MI_DV_525_422_* / MI_DV_625_422_* for the 4:2:2 systems: Y 720 x H, Cb 360 x H, Cr 360 x H).  The same rules
  * on alignment, batch size and kernel times; for MI_DV_SYS_525_60 the same output byte for byte.  MI_DV_ERR_ARG for an
  * unknown system. */
 int mi_dv_decode_batch_sys(mi_dv_ctx *c, int system, const void *d_frames, int n, void *d_pics);
 /* mi_dv_decode_frame for any system (for MI_DV_SYS_525_60 it is that function).  MI_DV_ERR_FORMAT for a frame that
- * does not announce `system` or is shorter than its frames; MI_DV_ERR_ARG for an unknown system.  One instance takes
- * frames of all four systems in any order. */
+ * does not announce `system` (for MI_DV_SYS_625_50_411: for which mi_dv_kind_of does not say so) or is shorter than its
+ * frames; MI_DV_ERR_ARG for an unknown system.  One instance takes frames of all five systems in any order. */
 int mi_dv_decode_frame_sys(mi_dv_ctx *c, int system, const uint8_t *frame, size_t len, uint8_t *const planes[3],
                            const int strides[3]);
 /* The kernels' own macroblock placement: macroblock m (0..4) of video segment `slot` (0..26) of DIF sequence `seq`.
  * 525/60: x in 32-pixel columns, y in 8-line rows (a column-22 macroblock is 16 x 16 pixels), as in the oracle;
- * 625/50: x, y in 16 x 16 macroblocks (0..44, 0..35).  The 4:2:2 systems: `seq` counts the frame's DIF sequences in
+ * 625/50: x, y in 16 x 16 macroblocks (0..44, 0..35).  625/50 4:1:1: seq 0..11, in the units of 525/60 (x in 32-pixel
+ * columns 0..22, y in 8-line rows 0..71).  The 4:2:2 systems: `seq` counts the frame's DIF sequences in
  * byte order, 0..19 / 0..23 (channel seq / 10, seq / 12); x in 16-pixel columns (0..44), y in 8-line rows (0..59 /
  * 0..71).  Host only; MI_DV_ERR_ARG for arguments out of range. */
 int mi_dv_mb_place(int system, int seq, int slot, int m, int *x, int *y);
