@@ -16,23 +16,20 @@
 
 using namespace midv;
 
-static_assert(MI_DV_FRAME_BYTES == kFrameBytes && MI_DV_PICTURE_BYTES == kPicBytes, "header and kernels agree");
-static_assert(MI_DV_625_FRAME_BYTES == Sys625::kFrameBytes && MI_DV_625_PICTURE_BYTES == Sys625::kPicBytes &&
-                  MI_DV_625_HEIGHT == Sys625::kH && MI_DV_625_CHROMA_WIDTH == Sys625::kCW &&
-                  MI_DV_625_CHROMA_HEIGHT == Sys625::kCH && MI_DV_SYS_525_60 == Sys525::kId && MI_DV_SYS_625_50 == Sys625::kId,
-              "header and kernels agree (625/50)");
-static_assert(MI_DV_SYS_525_60_422 == Sys525_422::kId && MI_DV_525_422_FRAME_BYTES == Sys525_422::kFrameBytes &&
-                  MI_DV_525_422_PICTURE_BYTES == Sys525_422::kPicBytes && MI_DV_HEIGHT == Sys525_422::kH &&
-                  MI_DV_SYS_625_50_422 == Sys625_422::kId && MI_DV_625_422_FRAME_BYTES == Sys625_422::kFrameBytes &&
-                  MI_DV_625_422_PICTURE_BYTES == Sys625_422::kPicBytes && MI_DV_625_HEIGHT == Sys625_422::kH &&
-                  MI_DV_422_CHROMA_WIDTH == Sys525_422::kCW && MI_DV_422_CHROMA_WIDTH == Sys625_422::kCW &&
-                  Sys525_422::kCH == Sys525_422::kH && Sys625_422::kCH == Sys625_422::kH && MI_DV_WIDTH == Sys525_422::kW &&
-                  MI_DV_WIDTH == Sys625_422::kW,
-              "header and kernels agree (4:2:2)");
-static_assert(MI_DV_SYS_625_50_411 == Sys625_411::kId && MI_DV_625_FRAME_BYTES == Sys625_411::kFrameBytes &&
-                  MI_DV_625_411_PICTURE_BYTES == Sys625_411::kPicBytes && MI_DV_625_411_CHROMA_WIDTH == Sys625_411::kCW &&
-                  MI_DV_625_HEIGHT == Sys625_411::kH && MI_DV_625_HEIGHT == Sys625_411::kCH && MI_DV_WIDTH == Sys625_411::kW,
-              "header and kernels agree (625/50 4:1:1)");
+// header and kernels agree: a system's id, frame, picture and planes as include/mi_dv.h states them
+template <class S, int Id, int FrameBytes, int PicBytes, int H, int CW, int CH>
+constexpr bool kAgrees = S::kId == Id && S::kFrameBytes == FrameBytes && S::kPicBytes == PicBytes && S::kW == MI_DV_WIDTH &&
+                         S::kH == H && S::kCW == CW && S::kCH == CH;
+static_assert(kAgrees<Sys525, MI_DV_SYS_525_60, MI_DV_FRAME_BYTES, MI_DV_PICTURE_BYTES, MI_DV_HEIGHT, MI_DV_CHROMA_WIDTH, MI_DV_HEIGHT> &&
+                  MI_DV_FRAME_BYTES == kFrameBytes && MI_DV_PICTURE_BYTES == kPicBytes, "header and kernels agree");
+static_assert(kAgrees<Sys625, MI_DV_SYS_625_50, MI_DV_625_FRAME_BYTES, MI_DV_625_PICTURE_BYTES, MI_DV_625_HEIGHT,
+                      MI_DV_625_CHROMA_WIDTH, MI_DV_625_CHROMA_HEIGHT>, "header and kernels agree (625/50)");
+static_assert(kAgrees<Sys625_411, MI_DV_SYS_625_50_411, MI_DV_625_FRAME_BYTES, MI_DV_625_411_PICTURE_BYTES, MI_DV_625_HEIGHT,
+                      MI_DV_625_411_CHROMA_WIDTH, MI_DV_625_HEIGHT>, "header and kernels agree (625/50 4:1:1)");
+static_assert(kAgrees<Sys525_422, MI_DV_SYS_525_60_422, MI_DV_525_422_FRAME_BYTES, MI_DV_525_422_PICTURE_BYTES, MI_DV_HEIGHT,
+                      MI_DV_422_CHROMA_WIDTH, MI_DV_HEIGHT>, "header and kernels agree (525/60 4:2:2)");
+static_assert(kAgrees<Sys625_422, MI_DV_SYS_625_50_422, MI_DV_625_422_FRAME_BYTES, MI_DV_625_422_PICTURE_BYTES, MI_DV_625_HEIGHT,
+                      MI_DV_422_CHROMA_WIDTH, MI_DV_625_HEIGHT>, "header and kernels agree (625/50 4:2:2)");
 static_assert(MI_DV_SYS_525_60_422 == (0x4 | 0) && MI_DV_SYS_625_50_422 == (0x4 | 1), "4:2:2 system = stype | DSF");
 
 namespace {
@@ -239,21 +236,78 @@ int one_frame_buffers(mi_dv_ctx* c, size_t frame_bytes, size_t pic_bytes) {
   return MI_DV_OK;
 }
 
-// one checked host frame of system S through the kernel into the caller's planes
+// ---- the five systems, once: what the entry points below need of each (generated from csrc/dv_common.h's Sys*) ----
+struct Row {
+  int id, frame_bytes, pic_bytes, w[3], h[3];  // the planes Y, Cb, Cr
+  int place_seqs;                              // the sequences mi_dv_mb_place takes: both channels', in byte order
+  // what the one-frame path's messages say: "<frames> frames have ...", "not a <what> (DSF ..., [APT ...,] stype ...<expected>)"
+  const char *frames, *what, *expected;
+  bool says_apt;
+  int (*launch)(mi_dv_ctx*, const char*, const void*, int, void*);
+  void (*place)(uint32_t, uint32_t, uint32_t, uint32_t&, uint32_t&);
+};
+// a host function of its own: the kernels' S::place stays what dv_common.h makes of it
 template <class S>
-int decode_one(mi_dv_ctx* c, const char* who, const uint8_t* frame, uint8_t* const planes[3], const int strides[3]) {
-  if (strides[0] < S::kW || strides[1] < S::kCW || strides[2] < S::kCW) return fail(c, MI_DV_ERR_ARG, "strides below the picture's width");
+void place_thunk(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x, uint32_t& y) {
+  S::place(seq, slot, m, x, y);
+}
+template <class S>
+constexpr Row row(const char* frames, const char* what, bool says_apt, const char* expected) {
+  return {S::kId, S::kFrameBytes, S::kPicBytes, {S::kW, S::kCW, S::kCW}, {S::kH, S::kCH, S::kCH}, S::kChans * S::kSeqs,
+          frames, what, expected, says_apt, launch<S>, place_thunk<S>};
+}
+constexpr Row kSystems[] = {
+    row<Sys525>("525/60", "525/60 25 Mbit/s DV frame", false, ""),
+    row<Sys625>("625/50", "625/50 25 Mbit/s 4:2:0 DV frame", true, ""),
+    row<Sys625_411>("625/50 4:1:1", "625/50 25 Mbit/s 4:1:1 (DVCPRO) DV frame", true, "; expected DSF 1, APT not 0, stype 0x00"),
+    row<Sys525_422>("525/60 50 Mbit/s 4:2:2", "525/60 50 Mbit/s 4:2:2 DV frame of 240000 bytes", false, "; expected DSF 0, stype 0x04"),
+    row<Sys625_422>("625/50 50 Mbit/s 4:2:2", "625/50 50 Mbit/s 4:2:2 DV frame of 288000 bytes", false, "; expected DSF 1, stype 0x04"),
+};
+const Row* find(int system) {  // nullptr: 2, 6 and the like are no systems
+  for (const Row& r : kSystems)
+    if (r.id == system) return &r;
+  return nullptr;
+}
+
+// dv_frame_profile (lib/dvframe.c:298-316) over the five systems: DSF = byte 3 bit 7, APT = byte 5 & 7, stype = byte
+// 80*5+48+3 & 0x1f.  stype 0 is 25 Mbit/s: 525/60 for DSF 0; for DSF 1 the IEC 4:2:0 profile with APT 0 and DVCPRO 625/50
+// 4:1:1 with any other (:303).  stype 4 is DVCPRO50, two DIF channels, 4:2:2 (:170-211): the system is stype | DSF.  -1: the
+// HD profiles, and a frame shorter than its system's
+int classify(const uint8_t* frame, size_t len) {
+  if (!frame || len < 80 * 6) return -1;
+  const int dsf = frame[3] >> 7, apt = frame[5] & 7, stype = frame[80 * 5 + 48 + 3] & 0x1f;
+  if (stype != 0 && stype != 0x4) return -1;
+  const int system = stype ? stype | dsf : !dsf ? MI_DV_SYS_525_60 : !apt ? MI_DV_SYS_625_50 : MI_DV_SYS_625_50_411;
+  return len >= (size_t)find(system)->frame_bytes ? system : -1;
+}
+
+// one host frame of system r, checked (arguments, length, announcement: in this order), through the kernel into the
+// caller's planes
+int decode_one(mi_dv_ctx* c, const Row& r, const char* who, const uint8_t* frame, size_t len, uint8_t* const planes[3],
+               const int strides[3]) {
+  if (!c || !frame || !planes || !strides || !planes[0] || !planes[1] || !planes[2])
+    return fail(c, MI_DV_ERR_ARG, "%s: NULL argument", who);
+  if (len < (size_t)r.frame_bytes)
+    return fail(c, MI_DV_ERR_FORMAT, "DIF frame of %zu bytes: %s frames have %d", len, r.frames, r.frame_bytes);
+  if (classify(frame, len) != r.id) {
+    const int dsf = frame[3] >> 7, apt = frame[5] & 7, stype = frame[80 * 5 + 48 + 3] & 0x1f;
+    char seen[64];
+    if (r.says_apt) snprintf(seen, sizeof seen, "DSF %d, APT %d, stype 0x%02x", dsf, apt, stype);
+    else snprintf(seen, sizeof seen, "DSF %d, stype 0x%02x", dsf, stype);
+    return fail(c, MI_DV_ERR_FORMAT, "not a %s (%s%s)", r.what, seen, r.expected);
+  }
+  if (strides[0] < r.w[0] || strides[1] < r.w[1] || strides[2] < r.w[2]) return fail(c, MI_DV_ERR_ARG, "strides below the picture's width");
   DVCHK(c, hipSetDevice(c->device));
-  int rc = one_frame_buffers(c, S::kFrameBytes, S::kPicBytes);
+  int rc = one_frame_buffers(c, (size_t)r.frame_bytes, (size_t)r.pic_bytes);
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, S::kFrameBytes, hipMemcpyHostToDevice, c->stream));
-  rc = launch<S>(c, who, c->d_frame, 1, c->d_pic);
+  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, (size_t)r.frame_bytes, hipMemcpyHostToDevice, c->stream));
+  rc = r.launch(c, who, c->d_frame, 1, c->d_pic);
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipMemcpyAsync(c->h_pic, c->d_pic, S::kPicBytes, hipMemcpyDeviceToHost, c->stream));
+  DVCHK(c, hipMemcpyAsync(c->h_pic, c->d_pic, (size_t)r.pic_bytes, hipMemcpyDeviceToHost, c->stream));
   DVCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* src = c->h_pic;
   for (int pl = 0; pl < 3; pl++) {
-    const int w = pl ? S::kCW : S::kW, h = pl ? S::kCH : S::kH;
+    const int w = r.w[pl], h = r.h[pl];
     for (int y = 0; y < h; y++) memcpy(planes[pl] + (size_t)y * strides[pl], src + (size_t)y * w, (size_t)w);
     src += (size_t)w * h;
   }
@@ -268,12 +322,9 @@ int mi_dv_decode_batch(mi_dv_ctx* c, const void* d_frames, int n, void* d_pics) 
 }
 
 int mi_dv_decode_batch_sys(mi_dv_ctx* c, int system, const void* d_frames, int n, void* d_pics) {
-  if (system == MI_DV_SYS_525_60) return launch<Sys525>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
-  if (system == MI_DV_SYS_625_50) return launch<Sys625>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
-  if (system == MI_DV_SYS_625_50_411) return launch<Sys625_411>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
-  if (system == MI_DV_SYS_525_60_422) return launch<Sys525_422>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
-  if (system == MI_DV_SYS_625_50_422) return launch<Sys625_422>(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
-  return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_batch_sys: unknown system %d", system);
+  const Row* r = find(system);
+  if (!r) return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_batch_sys: unknown system %d", system);
+  return r->launch(c, "mi_dv_decode_batch_sys", d_frames, n, d_pics);
 }
 
 int mi_dv_kernel_times(mi_dv_ctx* c, float* total_ms, int* launches) {
@@ -301,96 +352,36 @@ size_t mi_dv_copy_tables(void* out, size_t cap) {
 }
 
 int mi_dv_decode_frame(mi_dv_ctx* c, const uint8_t* frame, size_t len, uint8_t* const planes[3], const int strides[3]) {
-  if (!c || !frame || !planes || !strides || !planes[0] || !planes[1] || !planes[2])
-    return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame: NULL argument");
-  if (len < (size_t)kFrameBytes) return fail(c, MI_DV_ERR_FORMAT, "DIF frame of %zu bytes: 525/60 frames have %d", len, kFrameBytes);
-  // dv_frame_profile (lib/dvframe.c:298-316): DSF = byte 3 bit 7, stype = byte 80*5+48+3 & 0x1f; only 525/60 25 Mbit/s here
-  if ((frame[3] & 0x80) || (frame[80 * 5 + 48 + 3] & 0x1f) != 0)
-    return fail(c, MI_DV_ERR_FORMAT, "not a 525/60 25 Mbit/s DV frame (DSF %d, stype 0x%02x)", frame[3] >> 7, frame[80 * 5 + 48 + 3] & 0x1f);
-  return decode_one<Sys525>(c, "mi_dv_decode_frame", frame, planes, strides);
-}
-
-int mi_dv_system_of(const uint8_t* frame, size_t len) {
-  // dv_frame_profile (lib/dvframe.c:298-316): DSF = byte 3 bit 7, APT = byte 5 & 7, stype = byte 80*5+48+3 & 0x1f
-  if (!frame || len < 80 * 6) return -1;
-  const int dsf = frame[3] >> 7, apt = frame[5] & 7, stype = frame[80 * 5 + 48 + 3] & 0x1f;
-  if (stype != 0) return -1;  // DVCPRO50 (mi_dv_profile_of knows it) and the HD profiles
-  if (dsf == 0) return len >= (size_t)Sys525::kFrameBytes ? MI_DV_SYS_525_60 : -1;
-  if (apt != 0) return -1;  // DVCPRO 625/50 4:1:1 (lib/dvframe.c:303)
-  return len >= (size_t)Sys625::kFrameBytes ? MI_DV_SYS_625_50 : -1;
-}
-
-int mi_dv_profile_of(const uint8_t* frame, size_t len) {
-  if (!frame || len < 80 * 6) return -1;
-  const int dsf = frame[3] >> 7, stype = frame[80 * 5 + 48 + 3] & 0x1f;
-  if (stype == 0x4) {  // DVCPRO50: two DIF channels, 4:2:2 (lib/dvframe.c:170-211)
-    if (dsf == 0) return len >= (size_t)Sys525_422::kFrameBytes ? MI_DV_SYS_525_60_422 : -1;
-    return len >= (size_t)Sys625_422::kFrameBytes ? MI_DV_SYS_625_50_422 : -1;
-  }
-  return mi_dv_system_of(frame, len);
-}
-
-int mi_dv_kind_of(const uint8_t* frame, size_t len) {
-  // lib/dvframe.c:303: DSF 1 with stype 0 is the IEC 4:2:0 profile for APT 0 and DVCPRO 625/50 4:1:1 for any other APT
-  if (!frame || len < 80 * 6) return -1;
-  const int dsf = frame[3] >> 7, apt = frame[5] & 7, stype = frame[80 * 5 + 48 + 3] & 0x1f;
-  if (dsf == 1 && stype == 0 && apt != 0) return len >= (size_t)Sys625_411::kFrameBytes ? MI_DV_SYS_625_50_411 : -1;
-  return mi_dv_profile_of(frame, len);
+  return decode_one(c, *find(MI_DV_SYS_525_60), "mi_dv_decode_frame", frame, len, planes, strides);
 }
 
 int mi_dv_decode_frame_sys(mi_dv_ctx* c, int system, const uint8_t* frame, size_t len, uint8_t* const planes[3],
                            const int strides[3]) {
-  if (system == MI_DV_SYS_525_60) return mi_dv_decode_frame(c, frame, len, planes, strides);
-  if (system != MI_DV_SYS_625_50 && system != MI_DV_SYS_625_50_411 && system != MI_DV_SYS_525_60_422 &&
-      system != MI_DV_SYS_625_50_422)
-    return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame_sys: unknown system %d", system);
-  if (!c || !frame || !planes || !strides || !planes[0] || !planes[1] || !planes[2])
-    return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame_sys: NULL argument");
-  if (system == MI_DV_SYS_625_50) {
-    using S = Sys625;
-    if (len < (size_t)S::kFrameBytes) return fail(c, MI_DV_ERR_FORMAT, "DIF frame of %zu bytes: 625/50 frames have %d", len, S::kFrameBytes);
-    if (mi_dv_system_of(frame, len) != MI_DV_SYS_625_50)
-      return fail(c, MI_DV_ERR_FORMAT, "not a 625/50 25 Mbit/s 4:2:0 DV frame (DSF %d, APT %d, stype 0x%02x)", frame[3] >> 7,
-                  frame[5] & 7, frame[80 * 5 + 48 + 3] & 0x1f);
-    return decode_one<S>(c, "mi_dv_decode_frame_sys", frame, planes, strides);
-  }
-  if (system == MI_DV_SYS_625_50_411) {
-    using S = Sys625_411;
-    if (len < (size_t)S::kFrameBytes)
-      return fail(c, MI_DV_ERR_FORMAT, "DIF frame of %zu bytes: 625/50 4:1:1 frames have %d", len, S::kFrameBytes);
-    if (mi_dv_kind_of(frame, len) != MI_DV_SYS_625_50_411)
-      return fail(c, MI_DV_ERR_FORMAT, "not a 625/50 25 Mbit/s 4:1:1 (DVCPRO) DV frame (DSF %d, APT %d, stype 0x%02x; expected DSF 1, "
-                  "APT not 0, stype 0x00)", frame[3] >> 7, frame[5] & 7, frame[80 * 5 + 48 + 3] & 0x1f);
-    return decode_one<S>(c, "mi_dv_decode_frame_sys", frame, planes, strides);
-  }
-  // the 50 Mbit/s systems: DSF = byte 3 bit 7, stype = byte 80*5+48+3 & 0x1f must be 0x4 (lib/dvframe.c:298-316)
-  const bool pal = system == MI_DV_SYS_625_50_422;
-  const char* name = pal ? "625/50" : "525/60";
-  const int need = pal ? Sys625_422::kFrameBytes : Sys525_422::kFrameBytes;
-  if (len < (size_t)need)
-    return fail(c, MI_DV_ERR_FORMAT, "DIF frame of %zu bytes: %s 50 Mbit/s 4:2:2 frames have %d", len, name, need);
-  if (mi_dv_profile_of(frame, len) != system)
-    return fail(c, MI_DV_ERR_FORMAT, "not a %s 50 Mbit/s 4:2:2 DV frame of %d bytes (DSF %d, stype 0x%02x; expected DSF %d, stype 0x04)",
-                name, need, frame[3] >> 7, frame[80 * 5 + 48 + 3] & 0x1f, pal ? 1 : 0);
-  if (pal) return decode_one<Sys625_422>(c, "mi_dv_decode_frame_sys", frame, planes, strides);
-  return decode_one<Sys525_422>(c, "mi_dv_decode_frame_sys", frame, planes, strides);
+  if (system == MI_DV_SYS_525_60) return mi_dv_decode_frame(c, frame, len, planes, strides);  // under its own name
+  const Row* r = find(system);
+  if (!r) return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_frame_sys: unknown system %d", system);
+  return decode_one(c, *r, "mi_dv_decode_frame_sys", frame, len, planes, strides);
+}
+
+// the three queries are one classification, each with the systems it was written to know (include/mi_dv.h)
+int mi_dv_kind_of(const uint8_t* frame, size_t len) { return classify(frame, len); }
+
+int mi_dv_profile_of(const uint8_t* frame, size_t len) {
+  const int k = classify(frame, len);
+  return k == MI_DV_SYS_625_50_411 ? -1 : k;
+}
+
+int mi_dv_system_of(const uint8_t* frame, size_t len) {
+  const int k = classify(frame, len);
+  return k == MI_DV_SYS_525_60 || k == MI_DV_SYS_625_50 ? k : -1;
 }
 
 int mi_dv_mb_place(int system, int seq, int slot, int m, int* x, int* y) {
-  const int seqs = system == MI_DV_SYS_525_60       ? Sys525::kSeqs
-                   : system == MI_DV_SYS_625_50     ? Sys625::kSeqs
-                   : system == MI_DV_SYS_625_50_411 ? Sys625_411::kSeqs
-                   : system == MI_DV_SYS_525_60_422 ? 2 * Sys525_422::kSeqs  // (both channels' sequences, in byte order)
-                   : system == MI_DV_SYS_625_50_422 ? 2 * Sys625_422::kSeqs
-                                                    : 0;
-  if (!x || !y || seq < 0 || seq >= seqs || slot < 0 || slot >= 27 || m < 0 || m >= 5)
+  const Row* r = find(system);
+  if (!x || !y || !r || seq < 0 || seq >= r->place_seqs || slot < 0 || slot >= 27 || m < 0 || m >= 5)
     return fail(nullptr, MI_DV_ERR_ARG, "mi_dv_mb_place: system %d, sequence %d, segment %d, macroblock %d out of range", system, seq, slot, m);
   uint32_t ux, uy;
-  if (system == MI_DV_SYS_525_60) Sys525::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
-  else if (system == MI_DV_SYS_625_50) Sys625::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
-  else if (system == MI_DV_SYS_625_50_411) Sys625_411::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
-  else if (system == MI_DV_SYS_525_60_422) Sys525_422::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
-  else Sys625_422::place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
+  r->place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
   *x = (int)ux;
   *y = (int)uy;
   return MI_DV_OK;

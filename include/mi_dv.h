@@ -21,13 +21,13 @@
  * container.  The arithmetic is stated in oracle/dv_oracle.c (written from the published format, from memory); the
  * GPU path reproduces THAT bit for bit.  Pictures of a real DV stream will look right only as far as that statement
  * matches the standard's tables.  The 625/50 layout (the number of DIF sequences, the macroblock shuffle, the 4:2:0
- * block placement: DESIGN.md section 9) is written from the published format too and is just as unpinned; its checker,
- * tests/dv625.py, moves whole video segments between 625/50 and 525/60 frames around the unchanged oracle.  The 4:2:2
+ * block placement: DESIGN.md section 9) is written from the published format too and is just as unpinned.  The 4:2:2
  * layout (two channels back to back, areas 1 and 3 of the compressed macroblock without pixels, 16 x 8 macroblocks, the
  * super-block row 2 row + channel: DESIGN.md section 9.3) is this repository's reading of SMPTE 314M, unpinned in the
- * same way; its checker is tests/dv422.py.  The 625/50 4:1:1 layout (the 625/50 frame, the 525/60 macroblocks, right-edge
- * column and shuffle with 12 sequences as the modulus: DESIGN.md section 9.4) is a reading of SMPTE 314M from memory and
- * the least certain of all, unpinned in the same way; its checker is tests/dv411p.py.
+ * same way.  The 625/50 4:1:1 layout (the 625/50 frame, the 525/60 macroblocks, right-edge column and shuffle with 12
+ * sequences as the modulus: DESIGN.md section 9.4) is a reading of SMPTE 314M from memory and the least certain of all,
+ * unpinned in the same way.  One checker, tests/dvsys.py, states all four layouts: it moves whole video segments between
+ * a system's frames and 525/60 frames around the unchanged oracle.
  */
 #ifndef MI_DV_H
 #define MI_DV_H

@@ -14,8 +14,8 @@ import subprocess
 
 import numpy as np
 
-import dv625 as P
 import dvlib as D
+import dvsys as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(os.environ.get("MI_SAN_LIBDIR") or os.path.join(ROOT, "oracle"), "libdv_float.so")
@@ -151,7 +151,7 @@ def segment_qnos(dif):
     return np.array([dif[D.video_block_offset(s // 27, 5 * (s % 27)) + 3] & 15 for s in range(SEGMENTS)], np.uint8)
 
 
-# ---- 625/50: the same codec functions behind tests/dv625.py's segment moves ----
+# ---- 625/50: the same codec functions behind tests/dvsys.py's segment moves ----
 def decode625_info(frame):
     outs, fins = [], []
 
@@ -160,12 +160,12 @@ def decode625_info(frame):
         outs.append(out)
         fins.append(fin)
         return pic
-    pic = P.decode(frame, decode525=one)
+    pic = S.decode(S.SYS_625_50, frame, decode525=one)
     return pic, sum(outs), tuple(int(x) for x in np.sum(fins, axis=0))
 
 
 def encode625(pic, flags=3):
-    return P.encode(pic, flags, encode525=encode)
+    return S.encode(S.SYS_625_50, pic, flags, encode525=encode)
 
 
 # ---- comparison ----
@@ -320,23 +320,23 @@ def _block_map():
         for m in range(5):
             lib().dvf_mb_place(s // 27, s % 27, m, C.byref(x), C.byref(y))
             for j in range(6):
-                idx[(5 * s + m) * 6 + j] = P._block_525(x.value, y.value, j)
+                idx[(5 * s + m) * 6 + j] = S.block411(x.value, y.value, j, D.W, D.H, D.CW)
     return idx
 
 
 @functools.lru_cache(None)
 def picture(system, amp):
-    return D.synth(0, SEEDS["picture_seed"] + amp, amp) if system == 525 else P.synth625(0, SEEDS["picture_seed"] + amp, amp)
+    return S.synth(S.SYS_525_60 if system == 525 else S.SYS_625_50, 0, SEEDS["picture_seed"] + amp, amp)
 
 
 @functools.lru_cache(None)
 def frames(system, family):
     """the frames of a family, three encoders apart: 'a' the oracle's encoder, 'b' the plain encoder, on the same
-    synthetic pictures; 'c' symbol-written.  625/50 frames carry the same codec's segments (tests/dv625.py)."""
+    synthetic pictures; 'c' symbol-written.  625/50 frames carry the same codec's segments (tests/dvsys.py)."""
     pics = PICTURES_525 if system == 525 else PICTURES_625
     if family == "a":
-        enc = D.encode if system == 525 else P.encode
-        return [enc(picture(system, amp), flags) for amp, flags in pics]
+        sys_ = S.SYS_525_60 if system == 525 else S.SYS_625_50
+        return [S.encode(sys_, picture(system, amp), flags) for amp, flags in pics]
     if family == "b":
         enc = encode if system == 525 else encode625
         return [enc(picture(system, amp), flags) for amp, flags in pics]
@@ -344,11 +344,11 @@ def frames(system, family):
     if system == 525:
         return [symbol_frame(seed)[0] for seed in SEEDS["symbol_frames"]]
     a, b = (symbol_frame(seed)[0] for seed in SEEDS["symbol_frames"])
-    return [P.pack(np.concatenate([a, b])), P.pack(np.concatenate([b, a]))]
+    return [S.pack(S.SYS_625_50, np.concatenate([a, b])), S.pack(S.SYS_625_50, np.concatenate([b, a]))]
 
 
 def oracle_decode(system, frame):
-    return D.decode(frame) if system == 525 else P.decode(frame)
+    return S.decode(S.SYS_525_60 if system == 525 else S.SYS_625_50, frame)
 
 
 def float_decode_info(system, frame):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Writes tests/golden/dv411p_float_bounds.json: how far the fixed-point DV statement (oracle/dv_oracle.c, dvo_*) is
 from the floating-point one (oracle/dv_float.c, dvf_*) on whole frames of DVCPRO 625/50 4:1:1 (system 3), both through
-the segment moves of tests/dv411p.py — on exactly the seeded frames this module builds for tests/test_dv411p_cpu.py and
+the segment moves of tests/dvsys.py — on exactly the seeded frames this module builds for tests/test_dv411p_cpu.py and
 tests/test_gpu_dv411p.py.  The rule is make_dv_float_bounds.py's: deviation = oracle pixel minus
 float pixel clipped to 0..255, unrounded; a bound is the measured worst case rounded up to the next 0.25 level
 (absolute) or 0.01 level (mean signed deviation of a frame), with no margin; the reference is the float statement,
@@ -22,9 +22,10 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-import dv411p as P  # noqa: E402
 import dvfloat as F  # noqa: E402
+import dvsys as S  # noqa: E402
 
+SYSTEM = S.SYS_625_50_411
 BOUNDS = os.path.join(HERE, "dv411p_float_bounds.json")
 STEP = {"abs": 0.25, "mean": 0.01}
 # (noise amplitude, encoder flags) of the pictures: those of 625/50 4:2:0 in tests/dvfloat.py
@@ -34,7 +35,7 @@ FAMILIES = "abc"
 
 @functools.lru_cache(None)
 def picture(amp):
-    return P.synth(0, F.SEEDS["picture_seed"] + amp, amp)
+    return S.synth(SYSTEM, 0, F.SEEDS["picture_seed"] + amp, amp)
 
 
 COUNT = {"a": len(PICTURES), "b": len(PICTURES), "c": 2}
@@ -45,15 +46,15 @@ def frame(family, i):
     """frame i of a family (tests/dvfloat.py: frames), for system 3"""
     if family in ("a", "b"):
         amp, flags = PICTURES[i]
-        return P.encode(picture(amp), flags, encode525=None if family == "a" else F.encode)
+        return S.encode(SYSTEM, picture(amp), flags, encode525=None if family == "a" else F.encode)
     assert family == "c"
     a, b = (F.symbol_frame(seed)[0] for seed in F.SEEDS["symbol_frames"])
-    return P.pack(np.concatenate([a, b] if i == 0 else [b, a]))
+    return S.pack(SYSTEM, np.concatenate([a, b] if i == 0 else [b, a]))
 
 
 def float_decode_info(frame):
     """(unrounded picture, blocks outside the fixed-point range, blocks that ended in pass 1/2/3/never) of the float
-    statement behind tests/dv411p.py's segment moves (tests/dvfloat.py: decode625_info)"""
+    statement behind tests/dvsys.py's segment moves (tests/dvfloat.py: decode625_info)"""
     outs, fins = [], []
 
     def one(host):
@@ -61,7 +62,7 @@ def float_decode_info(frame):
         outs.append(out)
         fins.append(fin)
         return pic
-    pic = P.decode(frame, decode525=one)
+    pic = S.decode(SYSTEM, frame, decode525=one)
     return pic, sum(outs), tuple(int(x) for x in np.sum(fins, axis=0))
 
 
@@ -70,7 +71,7 @@ def reference(family, i):
     """(frame i of a family, the oracle's picture, the float statement's picture, blocks out of range), computed once"""
     fr = frame(family, i)
     pic, n_out, _ = float_decode_info(fr)
-    return fr, P.decode(fr), pic, n_out
+    return fr, S.decode(SYSTEM, fr), pic, n_out
 
 
 def references(family):
@@ -87,7 +88,7 @@ def r4(x):
 
 
 def text():
-    out = {"system": P.SYS_625_50_411, "seeds": F.SEEDS, "pictures": PICTURES, "step": STEP,
+    out = {"system": SYSTEM, "seeds": F.SEEDS, "pictures": PICTURES, "step": STEP,
            "measured": {"frames": {}}, "bounds": {"frames": {}}}
     for fam in FAMILIES:
         worst, mean, n_out = 0.0, 0.0, 0

@@ -1,11 +1,14 @@
 /*
  * dv_stream_harness.c — drives csrc/video_dv_mi355x.c the way lib/video.c drives a bgav_video_decoder_t
  * (bgav_video_start: lib/video.c:375-463; read_video_copy: :279-312), for DV streams whose pixel format the
- * demultiplexer set (lib/dvframe.c:490-500) — which plugin_harness.c cannot express.  Only the DV decoder is registered.
+ * demultiplexer set (lib/dvframe.c:490-500).  Only the DV decoder is registered.  The decoder takes a 720 x 576
+ * GAVL_YUV_411_P stream only when the environment holds MI_DV_625_411=1; this program passes its environment on unchanged
+ * and sets nothing itself, so the caller decides.  PARITY UNPINNED: see include/mi_dv.h.
  *
- *   dv_stream_harness <packets.bin> <image_w> <image_h> <411|420|none> <out.bin> [skip_every=N] [pad=P]
+ *   dv_stream_harness <packets.bin> <image_w> <image_h> <411|420|422|none> <out.bin> [skip_every=N] [pad=P]
  *
- *   411 / 420 / none  the stream's pixel format before a decoder is chosen: GAVL_YUV_411_P, GAVL_YUV_420_P, or unset
+ *   411 / 420 / 422 / none  the stream's pixel format before a decoder is chosen: GAVL_YUV_411_P, GAVL_YUV_420_P,
+ *                     GAVL_YUV_422_P, or unset
  *   skip_every=N      every N-th frame is skipped (decode(s, NULL): the packet is consumed, no picture)
  *   pad=P             the caller's strides are the plane widths + P bytes
  *
@@ -67,13 +70,14 @@ void gavl_log(int level, const char *domain, const char *fmt, ...) {
 
 int main(int argc, char **argv) {
   if (argc < 6)
-    return fprintf(stderr, "usage: %s packets.bin w h 411|420|none out.bin [skip_every=N] [pad=P]\n", argv[0]), 1;
+    return fprintf(stderr, "usage: %s packets.bin w h 411|420|422|none out.bin [skip_every=N] [pad=P]\n", argv[0]), 1;
   const int iw = atoi(argv[2]), ih = atoi(argv[3]);
   int pixfmt;
   if (!strcmp(argv[4], "411")) pixfmt = GAVL_YUV_411_P;
   else if (!strcmp(argv[4], "420")) pixfmt = GAVL_YUV_420_P;
+  else if (!strcmp(argv[4], "422")) pixfmt = GAVL_YUV_422_P;
   else if (!strcmp(argv[4], "none")) pixfmt = 0;
-  else return fprintf(stderr, "pixel format: 411, 420 or none\n"), 1;
+  else return fprintf(stderr, "pixel format: 411, 420, 422 or none\n"), 1;
   int skip_every = 0, pad = 0;
   for (int i = 6; i < argc; i++) {
     if (sscanf(argv[i], "skip_every=%d", &skip_every) == 1) continue;
@@ -118,9 +122,9 @@ int main(int argc, char **argv) {
   if (!dec) return fprintf(stderr, "no video decoder accepted the stream\n"), 3;
   if (!dec->init(&s)) return fprintf(stderr, "decoder init failed\n"), 4;
 
-  /* the planes the decoder announced: 4:1:1 (525/60) or 4:2:0 (625/50) */
-  const int cw = fmt.pixelformat == GAVL_YUV_411_P ? iw / 4 : (iw + 1) / 2;
-  const int ch = fmt.pixelformat == GAVL_YUV_411_P ? ih : (ih + 1) / 2;
+  /* the planes the decoder announced: 4:1:1 (w / 4 x h: 525/60 and, opted in, 625/50), 4:2:0 (625/50) or 4:2:2 (w / 2 x h) */
+  const int cw = fmt.pixelformat == GAVL_YUV_411_P ? iw / 4 : fmt.pixelformat == GAVL_YUV_422_P ? iw / 2 : (iw + 1) / 2;
+  const int ch = fmt.pixelformat == GAVL_YUV_411_P || fmt.pixelformat == GAVL_YUV_422_P ? ih : (ih + 1) / 2;
   gavl_video_frame_t f;
   memset(&f, 0, sizeof f);
   f.strides[0] = iw + pad;
@@ -143,8 +147,8 @@ int main(int argc, char **argv) {
   }
   fclose(fo);
   dec->close(&s);
-  fprintf(stderr, "decoder: %s, format %s, frame %dx%d image %dx%d\n", dec->name, meta.format, fmt.frame_width,
-          fmt.frame_height, iw, ih);
+  fprintf(stderr, "decoder: %s, format %s, frame %dx%d image %dx%d chroma %dx%d\n", dec->name, meta.format, fmt.frame_width,
+          fmt.frame_height, iw, ih, cw, ch);
   fprintf(stderr, "%d frames\n", nframes);
   for (int i = 0; i < q.n; i++) free(q.pkts[i].buf.buf);
   free(q.pkts);

@@ -1,5 +1,5 @@
 """DVCPRO 625/50 4:1:1 (system 3) without a GPU: the kernels' macroblock placement (mi_dv_mb_place) against the test
-statement (tests/dv411p.py); the host-side check over all five decodable profiles (mi_dv_kind_of) next to the two older
+statement (tests/dvsys.py); the host-side check over all five decodable profiles (mi_dv_kind_of) next to the two older
 ones, which stay as they were; the statement's own round trip; the fixed-point oracle against the float statement in
 this layout, within tests/golden/dv411p_float_bounds.json.  PARITY UNPINNED: both statements of the layout are this
 repository's reading of SMPTE 314M, from memory."""
@@ -13,15 +13,16 @@ import sys
 import numpy as np
 import pytest
 
-import dv411p as P
 import dvfloat as F
 import dvlib as D
+import dvsys as S
 from pkg import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import make_dv411p_float_bounds as M  # noqa: E402
 
 ERR_ARG = -1
+G = S.geometry(S.SYS_625_50_411)
 
 
 @pytest.fixture(scope="module")
@@ -35,9 +36,9 @@ def _c_place(dv, system, seq, slot, m):
 
 
 def test_the_python_view_states_the_same_geometry(dv):
-    assert dv.SYS_625_50_411 == P.SYS_625_50_411 == 3
-    assert dv.geometry(3) == (P.FRAME_BYTES, P.PICTURE_BYTES, ((720, 576), (180, 576), (180, 576)))
-    assert (P.FRAME_BYTES, P.PICTURE_BYTES, P.SEGMENTS, P.MACROBLOCKS) == (144000, 622080, 324, 1620)
+    assert dv.SYS_625_50_411 == S.SYS_625_50_411 == 3
+    assert dv.geometry(3) == (G.frame_bytes, G.picture_bytes, ((720, 576), (180, 576), (180, 576)))
+    assert (G.frame_bytes, G.picture_bytes, G.segments, G.macroblocks) == (144000, 622080, 324, 1620)
 
 
 def test_411p_placement_is_the_statements_for_all_1620_macroblocks(dv):
@@ -46,7 +47,7 @@ def test_411p_placement_is_the_statements_for_all_1620_macroblocks(dv):
         for slot in range(27):
             for m in range(5):
                 rc, xy = _c_place(dv, 3, seq, slot, m)
-                assert rc == 0 and xy == P.mb_place(seq, slot, m), (seq, slot, m, rc, xy)
+                assert rc == 0 and xy == S.mb_place(3, seq, slot, m), (seq, slot, m, rc, xy)
                 assert dv.place_of(3, seq, slot, m) == xy
                 assert 0 <= xy[0] <= 22 and 0 <= xy[1] <= (70 if xy[0] == 22 else 71)
                 seen.add(xy)
@@ -75,11 +76,11 @@ def test_525_placement_is_unchanged_for_its_1350_macroblocks(dv):
 
 
 def test_the_statements_blocks_tile_the_picture_exactly_once():
-    src, dst, here, b525 = P.maps()  # asserts the tiling itself
-    assert dst.size == src.size == P.PICTURE_BYTES and np.array_equal(np.sort(dst), np.arange(P.PICTURE_BYTES))
+    src, dst, here, b525 = S.maps(3)  # asserts the tiling itself
+    assert dst.size == src.size == G.picture_bytes and np.array_equal(np.sort(dst), np.arange(G.picture_bytes))
     assert here.size == b525.size == 1620 * 80
     # lines 480..575 and columns 704..719 are reached (what 525/60 has not, and what it has at another plane base)
-    hit = np.zeros(P.PICTURE_BYTES, bool)
+    hit = np.zeros(G.picture_bytes, bool)
     hit[dst] = True
     assert hit[:720 * 576].reshape(576, 720)[480:, :].all() and hit[:720 * 576].reshape(576, 720)[:, 704:].all()
 
@@ -125,8 +126,8 @@ def test_kind_of_every_profile_and_every_apt(dv, dvframe):
 
 
 def test_statement_frames_announce_kind_3(dv):
-    f = P.encode(P.synth(0, 2, 6), 3)
-    assert f.size == P.FRAME_BYTES and dv.kind_of(f) == 3 and dv.profile_of(f) == -1 and dv.system_of(f) == -1
+    f = S.encode(3, S.synth(3, 0, 2, 6), 3)
+    assert f.size == G.frame_bytes and dv.kind_of(f) == 3 and dv.profile_of(f) == -1 and dv.system_of(f) == -1
     assert f[3] >> 7 == 1 and f[5] & 7 == 1 and f[80 * 5 + 48 + 3] & 0x1F == 0
     blocks = f.reshape(12, 150, 80)
     for seq in range(12):
@@ -136,7 +137,7 @@ def test_statement_frames_announce_kind_3(dv):
 def test_synth_puts_detail_where_the_layout_differs_from_525_60():
     for region, ys, xs, cys, cxs in (("bottom", slice(480, 576), slice(0, 720), slice(480, 576), slice(0, 180)),
                                      ("right", slice(0, 576), slice(704, 720), slice(0, 576), slice(176, 180))):
-        pic = P.synth(1, 3, 6, region=region)
+        pic = S.synth(3, 1, 3, 6, region=region)
         Y = pic[:720 * 576].reshape(576, 720)
         cb = pic[720 * 576:720 * 576 + 180 * 576].reshape(576, 180)
         cr = pic[720 * 576 + 180 * 576:].reshape(576, 180)
@@ -144,7 +145,7 @@ def test_synth_puts_detail_where_the_layout_differs_from_525_60():
             inside = np.zeros(plane.shape, bool)
             inside[rs, cs] = True
             assert (plane[~inside] == 128).all() and plane[inside].std() > 4, region
-    full = P.synth(1, 3, 6)[:720 * 576].reshape(576, 720)
+    full = S.synth(3, 1, 3, 6)[:720 * 576].reshape(576, 720)
     assert full[480:].std() > 20 and full[:, 704:].std() > 20
 
 
@@ -153,7 +154,7 @@ def _distinct_blocks(seed):
     (tests/test_dv625_cpu.py's picture at this system's plane sizes)"""
     rng = np.random.default_rng(seed)
     planes = []
-    for w, h in ((P.W, P.H), (P.CW, P.CH), (P.CW, P.CH)):
+    for w, h in ((G.w, G.h), (G.cw, G.ch), (G.cw, G.ch)):
         by, bx = np.mgrid[0:h // 8, 0:(w + 7) // 8]
         level = 40 + (3 * bx + 5 * by + rng.integers(0, 170, bx.shape)) % 170
         px = np.repeat(np.repeat(level, 8, 0), 8, 1)[:, :w]
@@ -167,12 +168,12 @@ def _block_means(pic):
     """the mean of every coded block: 8 x 8 everywhere, and the 4 x 8 halves of the split chroma blocks of column 22
     (chroma columns 176..179) one half at a time — a half is all that lies in one place there"""
     out = []
-    Y = pic[:P.W * P.H].reshape(P.H // 8, 8, P.W // 8, 8).astype(np.float64)
+    Y = pic[:G.w * G.h].reshape(G.h // 8, 8, G.w // 8, 8).astype(np.float64)
     out.append(Y.mean(axis=(1, 3)))
-    for off in (P.W * P.H, P.W * P.H + P.CW * P.CH):
-        plane = pic[off:off + P.CW * P.CH].reshape(P.CH, P.CW).astype(np.float64)
-        out.append(plane[:, :176].reshape(P.CH // 8, 8, 22, 8).mean(axis=(1, 3)))
-        out.append(plane[:, 176:].reshape(P.CH // 8, 8, 4).mean(axis=(1, 2)))
+    for off in (G.w * G.h, G.w * G.h + G.cw * G.ch):
+        plane = pic[off:off + G.cw * G.ch].reshape(G.ch, G.cw).astype(np.float64)
+        out.append(plane[:, :176].reshape(G.ch // 8, 8, 22, 8).mean(axis=(1, 3)))
+        out.append(plane[:, 176:].reshape(G.ch // 8, 8, 4).mean(axis=(1, 2)))
     return out
 
 
@@ -181,7 +182,7 @@ def test_statement_round_trip_keeps_every_block_in_place(flags):
     """DC survives the encoder's rate control: a block or plane put anywhere else (a row taken modulo 10, column 22's
     split chroma halves at the 480-line plane base, the Cb / Cr order, a wrong shuffle) moves a mean by far more than 4"""
     pic = _distinct_blocks(30 + flags)
-    got = P.decode(P.encode(pic, flags))
+    got = S.decode(3, S.encode(3, pic, flags))
     worst = 0.0
     for i, (a, b) in enumerate(zip(_block_means(got), _block_means(pic))):
         d = np.abs(a - b)
@@ -192,10 +193,10 @@ def test_statement_round_trip_keeps_every_block_in_place(flags):
 
 def test_statement_decodes_arbitrary_bytes_deterministically():
     rng = np.random.default_rng(8)
-    f = rng.integers(0, 256, P.FRAME_BYTES, dtype=np.uint8)
-    a, b = P.decode(f), P.decode(f.copy())
-    assert a.size == P.PICTURE_BYTES and a.dtype == np.uint8 and np.array_equal(a, b)
-    assert not np.array_equal(a, P.decode(np.zeros(P.FRAME_BYTES, np.uint8)))
+    f = rng.integers(0, 256, G.frame_bytes, dtype=np.uint8)
+    a, b = S.decode(3, f), S.decode(3, f.copy())
+    assert a.size == G.picture_bytes and a.dtype == np.uint8 and np.array_equal(a, b)
+    assert not np.array_equal(a, S.decode(3, np.zeros(G.frame_bytes, np.uint8)))
 
 
 # ---- the fixed-point oracle against the float statement, in this layout ----

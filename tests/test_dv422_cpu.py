@@ -1,5 +1,5 @@
 """The 50 Mbit/s 4:2:2 DV systems without a GPU: the kernels' macroblock placement (mi_dv_mb_place) against the test
-statement (tests/dv422.py); the host-side profile check over all four decodable profiles (mi_dv_profile_of); what the
+statement (tests/dvsys.py); the host-side profile check over all four decodable profiles (mi_dv_profile_of); what the
 statement's encoder writes into the areas that carry no pixels; the statement's own round trip.  PARITY UNPINNED: both
 statements of the 4:2:2 layout are this repository's reading of SMPTE 314M."""
 import ctypes as C
@@ -10,8 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
-import dv422 as P
 import dvlib as D
+import dvsys as P
 from pkg import ROOT
 
 SYSTEMS = [P.SYS_525_60_422, P.SYS_625_50_422]
@@ -104,7 +104,7 @@ def _distinct_blocks(g, seed):
     (tests/test_dv625_cpu.py's picture at this system's plane sizes)"""
     rng = np.random.default_rng(seed)
     planes = []
-    for w, h in ((P.W, g.h), (P.CW, g.h), (P.CW, g.h)):
+    for w, h in ((g.w, g.h), (g.cw, g.h), (g.cw, g.h)):
         by, bx = np.mgrid[0:h // 8, 0:w // 8]
         level = 40 + (3 * bx + 5 * by + rng.integers(0, 170, bx.shape)) % 170
         px = np.repeat(np.repeat(level, 8, 0), 8, 1)
@@ -116,7 +116,7 @@ def _distinct_blocks(g, seed):
 
 def _block_means(g, pic):
     out = []
-    for off, w, h in ((0, P.W, g.h), (P.W * g.h, P.CW, g.h), (P.W * g.h + P.CW * g.h, P.CW, g.h)):
+    for off, w, h in ((0, g.w, g.h), (g.w * g.h, g.cw, g.h), (g.w * g.h + g.cw * g.h, g.cw, g.h)):
         plane = pic[off:off + w * h].reshape(h // 8, 8, w // 8, 8).astype(np.float64)
         out.append(plane.mean(axis=(1, 3)))
     return out
@@ -126,7 +126,7 @@ def _block_means(g, pic):
 @pytest.mark.parametrize("flags", [0, 1, 2, 3])
 def test_statement_frames_announce_their_system_and_leave_areas_1_and_3_empty(dv, system, flags):
     g = P.geometry(system)
-    f = P.encode(system, P.synth422(system, flags, 2, 6), flags)
+    f = P.encode(system, P.synth(system, flags, 2, 6), flags)
     assert f.size == g.frame_bytes and dv.profile_of(f) == system and dv.system_of(f) == -1
     assert f[3] >> 7 == g.dsf and f[80 * 5 + 48 + 3] & 0x1F == 4
     blocks = f.reshape(g.frame_seqs, 150, 80)

@@ -1,5 +1,5 @@
 """DV25 625/50 (IEC 4:2:0) without a GPU: the kernels' macroblock placement (mi_dv_mb_place) against the test statement
-(tests/dv625.py) and, for 525/60, against the oracle; the host-side profile check (mi_dv_system_of); the statement's own
+(tests/dvsys.py) and, for 525/60, against the oracle; the host-side profile check (mi_dv_system_of); the statement's own
 round trip.  PARITY UNPINNED: both statements of 625/50 are this repository's reading of the published format."""
 import ctypes as C
 import importlib
@@ -9,9 +9,11 @@ import subprocess
 import numpy as np
 import pytest
 
-import dv625 as P
 import dvlib as D
+import dvsys as S
 from pkg import ROOT
+
+G = S.geometry(S.SYS_625_50)
 
 
 @pytest.fixture(scope="module")
@@ -25,7 +27,7 @@ def test_625_placement_is_a_bijection_and_matches_the_statement(dv):
         for slot in range(27):
             for m in range(5):
                 x, y = dv.mb_place(dv.SYS_625_50, seq, slot, m)
-                assert (x, y) == P.mb_place(seq, slot, m), (seq, slot, m)
+                assert (x, y) == S.mb_place(S.SYS_625_50, seq, slot, m), (seq, slot, m)
                 seen[y, x] += 1
     assert (seen == 1).all()
 
@@ -81,13 +83,13 @@ def test_system_of_every_profile(dv, dvframe):
 
 
 def test_statement_frames_announce_625_50(dv):
-    f = P.encode(P.synth625(0, 2, 6), 3)
-    assert f.size == P.FRAME_BYTES and dv.system_of(f) == dv.SYS_625_50
+    f = S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, 0, 2, 6), 3)
+    assert f.size == G.frame_bytes and dv.system_of(f) == dv.SYS_625_50
 
 
 def _block_means(pic):
     out = []
-    for off, w, h in ((0, P.W, P.H), (P.W * P.H, P.CW, P.CH), (P.W * P.H + P.CW * P.CH, P.CW, P.CH)):
+    for off, w, h in ((0, G.w, G.h), (G.w * G.h, G.cw, G.ch), (G.w * G.h + G.cw * G.ch, G.cw, G.ch)):
         plane = pic[off:off + w * h].reshape(h // 8, 8, w // 8, 8).astype(np.float64)
         out.append(plane.mean(axis=(1, 3)))
     return out
@@ -97,7 +99,7 @@ def _distinct_blocks(seed):
     """every plane: a level per 8 x 8 block (a 2-D gradient plus a random offset), a gentle gradient and noise inside"""
     rng = np.random.default_rng(seed)
     planes = []
-    for w, h in ((P.W, P.H), (P.CW, P.CH), (P.CW, P.CH)):
+    for w, h in ((G.w, G.h), (G.cw, G.ch), (G.cw, G.ch)):
         by, bx = np.mgrid[0:h // 8, 0:w // 8]
         level = 40 + (3 * bx + 5 * by + rng.integers(0, 170, bx.shape)) % 170
         px = np.repeat(np.repeat(level, 8, 0), 8, 1)
@@ -112,7 +114,7 @@ def test_statement_round_trip_keeps_every_block_in_place(flags):
     """DC survives the encoder's rate control: a block or plane put anywhere else (column 22's split chroma halves, the
     Cb / Cr order, a wrong shuffle) moves a mean by far more than 4"""
     pic = _distinct_blocks(flags)
-    got = P.decode(P.encode(pic, flags))
+    got = S.decode(S.SYS_625_50, S.encode(S.SYS_625_50, pic, flags))
     for i, (a, b) in enumerate(zip(_block_means(got), _block_means(pic))):
         d = np.abs(a - b)
         assert d.max() <= 4, (flags, i, float(d.max()), np.unravel_index(d.argmax(), d.shape))
@@ -120,7 +122,7 @@ def test_statement_round_trip_keeps_every_block_in_place(flags):
 
 def test_statement_decodes_arbitrary_bytes_deterministically():
     rng = np.random.default_rng(8)
-    f = rng.integers(0, 256, P.FRAME_BYTES, dtype=np.uint8)
-    a, b = P.decode(f), P.decode(f.copy())
-    assert a.size == P.PICTURE_BYTES and np.array_equal(a, b)
-    assert not np.array_equal(a, P.decode(np.zeros(P.FRAME_BYTES, np.uint8)))
+    f = rng.integers(0, 256, G.frame_bytes, dtype=np.uint8)
+    a, b = S.decode(S.SYS_625_50, f), S.decode(S.SYS_625_50, f.copy())
+    assert a.size == G.picture_bytes and np.array_equal(a, b)
+    assert not np.array_equal(a, S.decode(S.SYS_625_50, np.zeros(G.frame_bytes, np.uint8)))

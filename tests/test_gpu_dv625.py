@@ -1,22 +1,21 @@
 """GPU parity of the DV25 625/50 (IEC 4:2:0) decoder — k_dv_decode<Sys625> through mi_dv_decode_batch_sys and
-mi_dv_decode_frame_sys — against the test statement tests/dv625.py (the unchanged oracle, segments moved), bit for bit;
+mi_dv_decode_frame_sys — against the test statement tests/dvsys.py (the unchanged oracle, segments moved), bit for bit;
 the refusals of the one-frame path; 525/60 unchanged behind the new entry points; the plugin seam with the stream's
-pixel format set (tests/harness/dv_stream_harness.c).  PARITY UNPINNED: see tests/dv625.py."""
+pixel format set (tests/harness/dv_stream_harness.c).  PARITY UNPINNED: see tests/dvsys.py."""
 import ctypes as C
 import hashlib
 import importlib
-import os
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
-import dv625 as P
 import dvlib as D
-from pkg import ROOT
+import dvsys as S
 
 pytestmark = pytest.mark.gpu
+G = S.geometry(S.SYS_625_50)
 
 
 @pytest.fixture(scope="module")
@@ -32,18 +31,15 @@ def dev(dv):
 
 
 def same(dev, dv, frames):
-    frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, P.FRAME_BYTES)
+    frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, G.frame_bytes)
     got = dev.decode_frames(frames, system=dv.SYS_625_50)
     for i, f in enumerate(frames):
-        want = P.decode(f)
-        if not np.array_equal(got[i], want):
-            bad = np.flatnonzero(got[i] != want)
-            raise AssertionError(f"frame {i}: {bad.size} bytes differ, first at {bad[0]} (got {got[i][bad[0]]}, want {want[bad[0]]})")
+        S.differ(S.SYS_625_50, got[i], S.decode(S.SYS_625_50, f), f"frame {i}")
 
 
 @pytest.mark.parametrize("amp,flags", [(0, 0), (4, 1), (8, 3), (16, 2), (40, 3), (90, 3)])
 def test_encoded_625_frames_decode_like_the_statement(dev, dv, amp, flags):
-    same(dev, dv, [P.encode(P.synth625(n, 5 + amp, amp), flags) for n in range(2)])
+    same(dev, dv, [S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, n, 5 + amp, amp), flags) for n in range(2)])
 
 
 def test_every_class_quantisation_number_and_mode_625(dev, dv):
@@ -51,7 +47,7 @@ def test_every_class_quantisation_number_and_mode_625(dev, dv):
     rng = np.random.default_rng(7)
     frames = []
     for n in range(3):
-        f = P.encode(P.synth625(n, 9, 10), 3).copy()
+        f = S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, n, 9, 10), 3).copy()
         for seq in range(12):
             for v in range(135):
                 o = D.video_block_offset(seq, v)
@@ -64,7 +60,7 @@ def test_every_class_quantisation_number_and_mode_625(dev, dv):
 
 def test_arbitrary_bytes_625(dev, dv):
     rng = np.random.default_rng(13)
-    frames = rng.integers(0, 256, (4, P.FRAME_BYTES), dtype=np.uint8)
+    frames = rng.integers(0, 256, (4, G.frame_bytes), dtype=np.uint8)
     frames[1] = 0
     frames[2] = 0xFF
     same(dev, dv, frames)
@@ -72,13 +68,13 @@ def test_arbitrary_bytes_625(dev, dv):
 
 @pytest.mark.parametrize("n", [1, 7, 64])
 def test_batch_sizes_625(dev, dv, n):
-    distinct = [P.encode(P.synth625(i, 31, 4 + 3 * i), 3) for i in range(min(n, 4))]
+    distinct = [S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, i, 31, 4 + 3 * i), 3) for i in range(min(n, 4))]
     same(dev, dv, [distinct[i % len(distinct)] for i in range(n)])
 
 
 def test_a_full_batch_of_1024_625_frames(dev, dv):
-    distinct = [P.encode(P.synth625(i, 17, 2 + 5 * (i % 8)), i % 4) for i in range(16)]
-    want = [hashlib.sha256(P.decode(f).tobytes()).hexdigest() for f in distinct]
+    distinct = [S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, i, 17, 2 + 5 * (i % 8)), i % 4) for i in range(16)]
+    want = [hashlib.sha256(S.decode(S.SYS_625_50, f).tobytes()).hexdigest() for f in distinct]
     frames = np.stack([distinct[i % 16] for i in range(1024)])
     got = dev.decode_frames(frames, system=dv.SYS_625_50)
     for i in range(1024):
@@ -86,8 +82,8 @@ def test_a_full_batch_of_1024_625_frames(dev, dv):
 
 
 def test_one_frame_path_625_with_padded_strides(dev, dv):
-    f = P.encode(P.synth625(3, 4, 12), 3)
-    want = P.decode(f)
+    f = S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, 3, 4, 12), 3)
+    want = S.decode(S.SYS_625_50, f)
     planes = dev.decode_frame(f, strides=(768, 400, 392), system=dv.SYS_625_50)
     assert np.array_equal(planes[0].reshape(576, 768)[:, :720].ravel(), want[:720 * 576])
     assert np.array_equal(planes[1].reshape(288, 400)[:, :360].ravel(), want[720 * 576:720 * 576 + 360 * 288])
@@ -100,7 +96,7 @@ def test_one_frame_path_625_with_padded_strides(dev, dv):
 
 
 def test_one_frame_path_refusals(dev, dv):
-    pal = P.encode(P.synth625(0, 1, 4), 0)
+    pal = S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, 0, 1, 4), 0)
     ntsc = D.encode(D.synth(0, 1, 4), 0)
     apt = pal.copy()
     apt[5] |= 1  # DVCPRO 625/50 4:1:1
@@ -112,13 +108,13 @@ def test_one_frame_path_refusals(dev, dv):
         dev.decode_frame(apt, system=dv.SYS_625_50)
     with pytest.raises(dv.MiDvError, match="143999 bytes"):
         dev.decode_frame(pal[:143999], system=dv.SYS_625_50)
-    assert np.array_equal(np.concatenate(dev.decode_frame(pal, system=dv.SYS_625_50)), P.decode(pal))  # still usable
+    assert np.array_equal(np.concatenate(dev.decode_frame(pal, system=dv.SYS_625_50)), S.decode(S.SYS_625_50, pal))  # still usable
 
 
 def test_an_unknown_system_is_an_argument_error(dev, dv):
     L, c = dev.L, dev.c
-    d_f, d_p = dev.alloc(P.FRAME_BYTES), dev.alloc(P.PICTURE_BYTES)
-    f = P.encode(P.synth625(0, 1, 4), 0)
+    d_f, d_p = dev.alloc(G.frame_bytes), dev.alloc(G.picture_bytes)
+    f = S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, 0, 1, 4), 0)
     planes = [np.zeros(720 * 576, np.uint8) for _ in range(3)]
     pp = (dv.u8p * 3)(*[p.ctypes.data_as(dv.u8p) for p in planes])
     st = (C.c_int * 3)(720, 360, 360)
@@ -155,66 +151,54 @@ def test_525_through_the_new_entry_point_is_unchanged(dev, dv):
 
 
 # ---- the plugin seam ----
-def _harness():
-    subprocess.run(["make", "-C", os.path.join(ROOT, "gmerlin-avdecoder_amd", "csrc")], check=True, capture_output=True)
-    return os.path.join(ROOT, "gmerlin-avdecoder_amd", "lib", "dv_stream_harness")
-
-
-def _packets(path, frames):
-    with open(path, "wb") as f:
-        for fr in frames:
-            f.write(struct.pack("<I", fr.size))
-            f.write(fr.tobytes())
-
-
 def test_625_stream_through_the_plugin_seam(tmp_path):
-    exe = _harness()
-    frames = [P.encode(P.synth625(n, 8, 5 + n), 3) for n in range(6)]
+    exe = S.harness()
+    frames = [S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, n, 8, 5 + n), 3) for n in range(6)]
     bad = D.encode(D.synth(0, 1, 4), 3)  # a 525/60 frame in the 625/50 stream
     pk, out = tmp_path / "p.bin", tmp_path / "o.bin"
-    _packets(pk, frames[:4] + [bad] + frames[4:])
+    S.packets(pk, frames[:4] + [bad] + frames[4:])
     r = subprocess.run([exe, str(pk), "720", "576", "420", str(out), "skip_every=3", "pad=24"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert "DV video decoder (MI355X)" in r.stderr and "format DV" in r.stderr and "frame 720x576" in r.stderr
     assert "625/50 frames have 144000" in r.stderr  # the foreign (short) frame ends the stream with a log line
-    rec = P.PICTURE_BYTES + 8
+    rec = G.picture_bytes + 8
     raw = np.fromfile(out, dtype=np.uint8)
     kept = [0, 1, 3]  # the 3rd packet is skipped, the 5th (the foreign frame) ends the stream
     assert raw.size == len(kept) * rec, r.stderr
     for i, k in enumerate(kept):
-        assert np.array_equal(raw[i * rec:i * rec + P.PICTURE_BYTES], P.decode(frames[k])), k
-        assert struct.unpack("<q", raw[i * rec + P.PICTURE_BYTES:(i + 1) * rec].tobytes())[0] == 1000 + 40 * k
+        assert np.array_equal(raw[i * rec:i * rec + G.picture_bytes], S.decode(S.SYS_625_50, frames[k])), k
+        assert struct.unpack("<q", raw[i * rec + G.picture_bytes:(i + 1) * rec].tobytes())[0] == 1000 + 40 * k
 
 
 def test_625_stream_ends_at_a_foreign_frame(tmp_path):
-    exe = _harness()
-    frames = [P.encode(P.synth625(n, 9, 6), 1) for n in range(3)]
-    bad = np.concatenate([D.encode(D.synth(0, 1, 4), 3), np.zeros(P.FRAME_BYTES - D.FRAME_BYTES, np.uint8)])  # DSF 0
+    exe = S.harness()
+    frames = [S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, n, 9, 6), 1) for n in range(3)]
+    bad = np.concatenate([D.encode(D.synth(0, 1, 4), 3), np.zeros(G.frame_bytes - D.FRAME_BYTES, np.uint8)])  # DSF 0
     pk, out = tmp_path / "p.bin", tmp_path / "o.bin"
-    _packets(pk, frames[:2] + [bad] + frames[2:])
+    S.packets(pk, frames[:2] + [bad] + frames[2:])
     r = subprocess.run([exe, str(pk), "720", "576", "420", str(out)], capture_output=True, text=True)
     assert r.returncode == 0 and "not a 625/50" in r.stderr, r.stderr
     raw = np.fromfile(out, dtype=np.uint8)
-    rec = P.PICTURE_BYTES + 8
+    rec = G.picture_bytes + 8
     assert raw.size == 2 * rec
     for i in range(2):
-        assert np.array_equal(raw[i * rec:i * rec + P.PICTURE_BYTES], P.decode(frames[i]))
+        assert np.array_equal(raw[i * rec:i * rec + G.picture_bytes], S.decode(S.SYS_625_50, frames[i]))
 
 
 @pytest.mark.parametrize("pixfmt", ["411", "none"])
 def test_other_720x576_streams_are_declined(tmp_path, pixfmt):
-    exe = _harness()
+    exe = S.harness()
     pk, out = tmp_path / "p.bin", tmp_path / "o.bin"
-    _packets(pk, [P.encode(P.synth625(0, 1, 4), 3)])
+    S.packets(pk, [S.encode(S.SYS_625_50, S.synth(S.SYS_625_50, 0, 1, 4), 3)])
     r = subprocess.run([exe, str(pk), "720", "576", pixfmt, str(out)], capture_output=True, text=True)
     assert r.returncode == 3, r.stderr
 
 
 def test_720x480_stream_still_decodes(tmp_path):
-    exe = _harness()
+    exe = S.harness()
     frames = [D.encode(D.synth(n, 4, 6), 3) for n in range(3)]
     pk, out = tmp_path / "p.bin", tmp_path / "o.bin"
-    _packets(pk, frames)
+    S.packets(pk, frames)
     r = subprocess.run([exe, str(pk), "720", "480", "none", str(out), "pad=8"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert "frame 720x480" in r.stderr

@@ -9,9 +9,9 @@ import importlib
 import numpy as np
 import pytest
 
-import dv625 as P
 import dvfloat as F
 import dvlib as D
+import dvsys as S
 
 pytestmark = pytest.mark.gpu
 B = F.bounds()
@@ -82,11 +82,11 @@ def test_every_scan_positions_gain_on_the_kernel(dev, dv, system):
         assert np.array_equal(got, D.decode(dif))
         pic525 = got
     else:
-        frame = P.pack(np.concatenate([dif, dif]))
+        frame = S.pack(S.SYS_625_50, np.concatenate([dif, dif]))
         got = dev.decode_frames(frame[None], system=dv.SYS_625_50)[0]
-        assert np.array_equal(got, P.decode(frame))
-        src, dst, _, _ = P.maps()
-        hosts = np.zeros(P.HOSTS * D.PICTURE_BYTES, np.uint8)
+        assert np.array_equal(got, S.decode(S.SYS_625_50, frame))
+        src, dst, _, _ = S.maps(S.SYS_625_50)
+        hosts = np.zeros(S.geometry(S.SYS_625_50).hosts * D.PICTURE_BYTES, np.uint8)
         hosts[src] = got[dst]
         pic525 = hosts[:D.PICTURE_BYTES]
     px = np.zeros((order.size, 64), np.uint8)

@@ -8,8 +8,7 @@ DVCPRO 625/50 4:1:1 and, as their yardsticks in the same session, the two older 
 pictures and tiled) are decoded into as many pictures in HBM by mi_dv_decode_batch_sys, once per step.  The time is the
 HIP-event time of the kernel launches (mi_dv_kernel_times).  Prints one JSON line: frames/s, ms per launch, GB/s where
 the bytes are the frames read plus the pictures written, the fraction of 8 TB/s, and a bit-exact check of every
-distinct frame against the checker (tests/dv422.py for 4:2:2, tests/dv411p.py for 625/50 4:1:1, tests/dv625.py for 625/50
-4:2:0, oracle/dv_oracle.c for 525/60).
+distinct frame against the checker (tests/dvsys.py; for 525/60 that is oracle/dv_oracle.c itself).
 PARITY UNPINNED.  The method and the line are tools/bench_dv625.py's, plus the video segments per frame and the time per
 segment: a 4:2:2 frame has twice the segments of the 25 Mbit/s frame of its line system, the same parse per segment and
 fewer transforms and stores, so it is compared with that system per segment, in one session.  The checker's encoder
@@ -18,7 +17,7 @@ segment, and more of them in the space areas 1 and 3 leave (pass 2, where one la
 `--content dv25` (4:2:2 systems only) takes that difference out: the frames' segments are those of the 525/60 bench's
 frames, byte for byte (areas 1 and 3 then hold ordinary blocks, which the decoder parses and drops), so the parse per
 segment IS the yardstick's.  625/50 4:1:1 (`--system 625_411`) takes both contents too: its own is the checker's encoder
-on tests/dv411p.py's pictures, `dv25` the 525/60 bench's segments byte for byte (324 of two such frames); its store forms
+on tests/dvsys.py's pictures, `dv25` the 525/60 bench's segments byte for byte (324 of two such frames); its store forms
 are 525/60's, so with that content the time per segment is to be compared with the 525/60 yardstick's."""
 import argparse
 import hashlib
@@ -47,36 +46,20 @@ def main():
     a = ap.parse_args()
     dv = importlib.import_module("gmerlin-avdecoder_amd.dv")
     import dvlib as D
-    import dv422 as Q
-    import dv625 as P
-    import dv411p as R
+    import dvsys as S
     system = {"525": dv.SYS_525_60, "625": dv.SYS_625_50, "625_411": dv.SYS_625_50_411, "525_422": dv.SYS_525_60_422, "625_422": dv.SYS_625_50_422}[a.system]
-    segments = {"525": 270, "625": 324, "625_411": 324, "525_422": 540, "625_422": 648}[a.system]
+    segments = S.geometry(system).segments
     fb, pb, _ = dv.geometry(system)
     n, k = a.frames, max(1, min(a.distinct, a.frames))
     if a.content == "dv25" and system not in (dv.SYS_525_60_422, dv.SYS_625_50_422, dv.SYS_625_50_411):
         ap.error("--content dv25 is for the 4:2:2 systems and 625/50 4:1:1")
-    if system in (dv.SYS_525_60_422, dv.SYS_625_50_422):
-        if a.content == "dv25":
-            hosts = Q.geometry(system).hosts
-            distinct = [Q.pack(system, np.concatenate([D.encode(D.synth(hosts * i + h, 7, 2 + 3 * (i % 12)), 3) for h in range(hosts)]))
-                        for i in range(k)]
-        else:
-            distinct = [Q.encode(system, Q.synth422(system, i, 7, 2 + 3 * (i % 12)), 3) for i in range(k)]
-        want = [hashlib.sha256(Q.decode(system, f).tobytes()).hexdigest() for f in distinct]
-    elif system == dv.SYS_625_50_411:
-        if a.content == "dv25":
-            distinct = [R.pack(np.concatenate([D.encode(D.synth(R.HOSTS * i + h, 7, 2 + 3 * (i % 12)), 3) for h in range(R.HOSTS)]))
-                        for i in range(k)]
-        else:
-            distinct = [R.encode(R.synth(i, 7, 2 + 3 * (i % 12)), 3) for i in range(k)]
-        want = [hashlib.sha256(R.decode(f).tobytes()).hexdigest() for f in distinct]
-    elif system == dv.SYS_625_50:
-        distinct = [P.encode(P.synth625(i, 7, 2 + 3 * (i % 12)), 3) for i in range(k)]
-        want = [hashlib.sha256(P.decode(f).tobytes()).hexdigest() for f in distinct]
+    if a.content == "dv25":
+        hosts = S.geometry(system).hosts
+        distinct = [S.pack(system, np.concatenate([D.encode(D.synth(hosts * i + h, 7, 2 + 3 * (i % 12)), 3) for h in range(hosts)]))
+                    for i in range(k)]
     else:
-        distinct = [D.encode(D.synth(i, 7, 2 + 3 * (i % 12)), 3) for i in range(k)]
-        want = [hashlib.sha256(D.decode(f).tobytes()).hexdigest() for f in distinct]
+        distinct = [S.encode(system, S.synth(system, i, 7, 2 + 3 * (i % 12)), 3) for i in range(k)]
+    want = [hashlib.sha256(S.decode(system, f).tobytes()).hexdigest() for f in distinct]
     frames = np.stack([distinct[i % k] for i in range(n)])
     dev = dv.MiDv(0)
     df, dp = dev.alloc(n * fb), dev.alloc(n * pb)

@@ -6,7 +6,7 @@
 pictures and tiled) are decoded into as many pictures in HBM by mi_dv_decode_batch_sys, once per step.  The time is the
 HIP-event time of the kernel launches (mi_dv_kernel_times).  Prints one JSON line: frames/s, ms per launch, GB/s where
 the bytes are the frames read plus the pictures written, the fraction of 8 TB/s, and a bit-exact check of every
-distinct frame against the checker (tests/dv625.py for 625/50, oracle/dv_oracle.c for 525/60).  PARITY UNPINNED.
+distinct frame against the checker (tests/dvsys.py; for 525/60 that is oracle/dv_oracle.c itself).  PARITY UNPINNED.
 Run both systems in one session to compare them per block (a 625/50 frame has 1.2 x the blocks of a 525/60 one)."""
 import argparse
 import hashlib
@@ -33,17 +33,12 @@ def main():
     ap.add_argument("--distinct", type=int, default=16)
     a = ap.parse_args()
     dv = importlib.import_module("gmerlin-avdecoder_amd.dv")
-    import dvlib as D
-    import dv625 as P
+    import dvsys as S
     system = dv.SYS_625_50 if a.system == "625" else dv.SYS_525_60
     fb, pb, _ = dv.geometry(system)
     n, k = a.frames, max(1, min(a.distinct, a.frames))
-    if system == dv.SYS_625_50:
-        distinct = [P.encode(P.synth625(i, 7, 2 + 3 * (i % 12)), 3) for i in range(k)]
-        want = [hashlib.sha256(P.decode(f).tobytes()).hexdigest() for f in distinct]
-    else:
-        distinct = [D.encode(D.synth(i, 7, 2 + 3 * (i % 12)), 3) for i in range(k)]
-        want = [hashlib.sha256(D.decode(f).tobytes()).hexdigest() for f in distinct]
+    distinct = [S.encode(system, S.synth(system, i, 7, 2 + 3 * (i % 12)), 3) for i in range(k)]
+    want = [hashlib.sha256(S.decode(system, f).tobytes()).hexdigest() for f in distinct]
     frames = np.stack([distinct[i % k] for i in range(n)])
     dev = dv.MiDv(0)
     df, dp = dev.alloc(n * fb), dev.alloc(n * pb)
