@@ -33,7 +33,21 @@ EXPORTS = ["mi_rtj_device_count", "mi_rtj_create", "mi_rtj_destroy", "mi_rtj_las
            "mi_rtj_plan_step_times", "mi_rtj_pipe_create", "mi_rtj_pipe_destroy", "mi_rtj_pipe_room",
            "mi_rtj_pipe_pending", "mi_rtj_pipe_submit", "mi_rtj_pipe_next", "mi_rtj_pipe_peek_tag", "mi_rtj_pipe_flush",
            "mi_rtj_pipe_profile", "mi_rtj_pipe_times", "mi_rtj_plan_set_runs", "mi_rtj_plan_run_times",
-           "mi_rtj_plan_run_stats"]
+           "mi_rtj_plan_run_stats", "mi_rtj_set_format", "mi_rtj_get_format", "mi_rtj_yuv422_to_rgb24"]
+
+# picture formats (mi_rtj_set_format): RTJ_YUV420 / RTJ_YUV422 / RTJ_RGB8 of the reference
+FMT_YUV420, FMT_YUV422, FMT_GREY = 0, 1, 2
+
+
+def plane_sizes(fmt, w, h):
+    """(bytes of Y, bytes of each chroma plane) of a w x h picture: chroma is w/2 x h/2 in 4:2:0, w/2 x h in 4:2:2, absent
+    in greyscale."""
+    return w * h, {FMT_YUV420: (w // 2) * (h // 2), FMT_YUV422: (w // 2) * h, FMT_GREY: 0}[fmt]
+
+
+def blocks_of(fmt, w, h):
+    """8x8 blocks of a w x h picture in stream order: 6 per 16x16 / 4 per 16x8 macroblock / 1 per block"""
+    return {FMT_YUV420: (w // 16) * (h // 16) * 6, FMT_YUV422: (w // 16) * (h // 8) * 4, FMT_GREY: (w // 8) * (h // 8)}[fmt]
 
 
 KERNELS = ("k_index_summarize", "k_index_resolve", "k_index_emit", "k_decode", "k_spec_walk", "k_spec_verify")
@@ -57,6 +71,9 @@ def load():
     L.mi_rtj_decode.argtypes = [vp, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int), C.c_int, C.c_int]
     L.mi_rtj_decode_nocopy.argtypes = [vp, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int)]
     L.mi_rtj_get_state.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mi_rtj_set_format.argtypes = [vp, C.c_int]
+    L.mi_rtj_get_format.argtypes = [vp]
+    L.mi_rtj_yuv422_to_rgb24.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t]
     L.mi_rtj_dev_alloc.argtypes = [vp, C.c_size_t]
     L.mi_rtj_dev_alloc.restype = vp
     L.mi_rtj_dev_free.argtypes = [vp, vp]
@@ -124,7 +141,13 @@ def get_tables(Q):
 class Plan:
     def __init__(self, owner, handle, n):
         self.owner, self.h, self.n = owner, handle, n
+        self.fmt = owner.format  # a plan takes the instance's format when it is created
         owner._plans.add(self)
+
+    def picture_bytes(self, w, h):
+        """bytes a w x h picture of this plan takes in the output buffer (Y, then the chroma planes, contiguous)"""
+        ysz, csz = plane_sizes(self.fmt, w, h)
+        return ysz + 2 * csz
 
     def close(self):
         if self.h:
@@ -290,10 +313,19 @@ class MiRtj:
         if rc != 0:
             raise MiRtjError(f"rc={rc}: " + self.L.mi_rtj_last_error(self.h).decode())
 
+    # -- picture format (RTjpeg_set_format) --
+    def set_format(self, fmt):
+        """FMT_YUV420 / FMT_YUV422 / FMT_GREY; before the first decode, plan or session (later: only the format it has)."""
+        self._chk(self.L.mi_rtj_set_format(self.h, int(fmt)))
+
+    @property
+    def format(self):
+        return self.L.mi_rtj_get_format(self.h)
+
     # -- one packet in, one frame out (decode_rtjpeg) --
     def decode(self, pkt, out=None, crop=None, strides=None):
         """pkt: uint8 array.  out: uint8 array receiving Y,U,V back to back (with `strides`, each plane
-        has its own row pitch).  Returns rc-checked None."""
+        has its own row pitch; 4:2:2: chroma planes of every line; greyscale: Y alone).  Returns rc-checked None."""
         pkt = np.ascontiguousarray(pkt, dtype=np.uint8)
         pp = pkt.ctypes.data_as(u8p)
         if out is None:
@@ -302,10 +334,17 @@ class MiRtj:
         w = int(pkt[6]) | (int(pkt[7]) << 8)
         h = int(pkt[8]) | (int(pkt[9]) << 8)
         cw, ch = crop if crop else (w, h)
+        fmt = self.format
         if strides is None:
             strides = (cw, (cw + 1) // 2, (cw + 1) // 2)
         ysz = strides[0] * ch
-        csz = strides[1] * ((ch + 1) // 2)
+        if fmt == FMT_GREY:
+            assert out.size >= ysz
+            planes = (u8p * 3)(C.cast(out.ctypes.data, u8p), None, None)
+            st = (C.c_int * 3)(strides[0], 0, 0)
+            self._chk(self.L.mi_rtj_decode(self.h, pp, pkt.size, planes, st, cw, ch))
+            return
+        csz = strides[1] * (ch if fmt == FMT_YUV422 else (ch + 1) // 2)
         assert out.size >= ysz + 2 * csz
         base = out.ctypes.data
         planes = (u8p * 3)(C.cast(base, u8p), C.cast(base + ysz, u8p), C.cast(base + ysz + csz, u8p))
@@ -313,7 +352,8 @@ class MiRtj:
         self._chk(self.L.mi_rtj_decode(self.h, pp, pkt.size, planes, st, cw, ch))
 
     def decode_nocopy(self, pkt):
-        """Returns (y, u, v) numpy views of the instance's pinned picture, valid until the next decode."""
+        """Returns (y, u, v) numpy views of the instance's pinned picture, valid until the next decode (greyscale:
+        u and v are None)."""
         pkt = np.ascontiguousarray(pkt, dtype=np.uint8)
         planes = (u8p * 3)()
         st = (C.c_int * 3)()
@@ -321,7 +361,11 @@ class MiRtj:
         w = int(pkt[6]) | (int(pkt[7]) << 8)
         h = int(pkt[8]) | (int(pkt[9]) << 8)
         mk = lambda p, n: np.ctypeslib.as_array(p, shape=(n,))
-        return mk(planes[0], w * h), mk(planes[1], w * h // 4), mk(planes[2], w * h // 4)
+        ysz, csz = plane_sizes(self.format, w, h)
+        if csz == 0:
+            assert not planes[1] and not planes[2] and st[1] == 0 and st[2] == 0
+            return mk(planes[0], ysz), None, None
+        return mk(planes[0], ysz), mk(planes[1], csz), mk(planes[2], csz)
 
     def pipe(self, depth=4, coded_w=0, coded_h=0):
         """A pipelined session (mi_rtj_pipe_*): packets in, pictures out in order, several in flight."""
@@ -392,6 +436,10 @@ class MiRtj:
     # -- colour stage (N2) --
     def to_rgb(self, fmt, w, h, n, d_planes, in_stride, d_rgb, row_pitch, out_stride):
         self._chk(self.L.mi_rtj_yuv420_to_rgb(self.h, fmt, w, h, n, d_planes, in_stride, d_rgb, row_pitch, out_stride))
+
+    def to_rgb422(self, w, h, n, d_planes, in_stride, d_rgb, row_pitch, out_stride):
+        """RTjpeg_yuv422rgb24: n frames of contiguous 4:2:2 planes to R, G, B bytes"""
+        self._chk(self.L.mi_rtj_yuv422_to_rgb24(self.h, w, h, n, d_planes, in_stride, d_rgb, row_pitch, out_stride))
 
     def copy_ceiling(self, d_src, d_dst, nbytes, reps=10):
         """GB/s (read + write) a plain streaming copy kernel sustains on this device."""

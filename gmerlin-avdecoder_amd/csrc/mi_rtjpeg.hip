@@ -22,6 +22,7 @@
 #include "rtj_decode_chroma.h"
 #include "rtj_decode_kernels.h"
 #include "rtj_encode_kernels.h"
+#include "rtj_format_kernels.h"
 #include "rtj_index_kernels.h"
 #include "rtj_runs_kernels.h"
 #include "rtj_spec_kernels.h"
@@ -53,6 +54,10 @@ struct mi_rtj_ctx {
   std::string err;
   // RTjpeg_t's header-driven state (lib/RTjpeg.c:3568-3579)
   int width = 0, height = 0, Q = 0;
+  // which arm of RTjpeg_decompress's switch the instance decodes (RTjpeg_set_format, lib/RTjpeg.c:2421): MI_RTJ_FMT_*.
+  // Fixed by the first decode, plan or session: the persistent picture below has one layout.
+  int fmt = 0;
+  bool fmt_fixed = false;
   // persistent picture of the one-packet path (priv->frame of lib/video_rtjpeg.c:31-35)
   uint8_t* d_frame = nullptr;
   size_t frame_bytes = 0;
@@ -71,6 +76,7 @@ struct mi_rtj_ctx {
 struct mi_rtj_plan {
   mi_rtj_ctx* ctx = nullptr;
   int n = 0;
+  int fmt = 0;                      // the instance's format when the plan was made (MI_RTJ_FMT_*)
   std::vector<FrameDev> h_frames;
   FrameDev* d_frames = nullptr;
   uint32_t* d_blkoff = nullptr;
@@ -291,7 +297,13 @@ bool device_is_gfx950(int dev) {
 // Returns the LUT row to use, or a negative error.
 int apply_header(mi_rtj_ctx* c, const uint8_t* hdr, int* w, int* h) {
   const int hw = hdr[6] | (hdr[7] << 8), hh = hdr[8] | (hdr[9] << 8), q = hdr[10];
-  if (hw <= 0 || hh <= 0 || (hw & 15) || (hh & 15))
+  if (c->fmt == MI_RTJ_FMT_YUV422) {  // the loops of lib/RTjpeg.c:2651-2653 step 8 lines and 16 columns
+    if (hw <= 0 || hh <= 0 || (hw & 15) || (hh & 7))
+      return fail(c, MI_RTJ_ERR_GEOMETRY, "packet header %dx%d: a 4:2:2 picture needs a positive width that is a multiple of 16 and a positive height that is a multiple of 8", hw, hh);
+  } else if (c->fmt == MI_RTJ_FMT_GREY) {  // lib/RTjpeg.c:2761-2763 step 8 lines and 8 columns
+    if (hw <= 0 || hh <= 0 || (hw & 7) || (hh & 7))
+      return fail(c, MI_RTJ_ERR_GEOMETRY, "packet header %dx%d: a greyscale picture needs a positive width and height that are multiples of 8", hw, hh);
+  } else if (hw <= 0 || hh <= 0 || (hw & 15) || (hh & 15))
     return fail(c, MI_RTJ_ERR_GEOMETRY, "packet header %dx%d: width and height must be positive multiples of 16", hw, hh);
   c->width = hw;
   c->height = hh;
@@ -316,13 +328,31 @@ int fill_frame(mi_rtj_ctx* c, const uint8_t* hdr, uint64_t pkt_off, uint32_t pkt
   f->h = (uint32_t)h;
   f->qidx = (uint32_t)q;
   f->blk_base = blk_base;
-  f->mbw = (uint32_t)w / 16;
-  f->nmb = f->mbw * ((uint32_t)h / 16);
-  if ((uint64_t)f->nmb * 6 * 64 + kAllocPad >= 0xFFFFFFFFull)  // block offsets and the walkers' positions are 32-bit
+  if (c->fmt == MI_RTJ_FMT_YUV422) {  // macroblock = 16x8 pixels: Y Y Cb Cr
+    f->mbw = (uint32_t)w / 16;
+    f->nmb = f->mbw * ((uint32_t)h / 8);
+  } else if (c->fmt == MI_RTJ_FMT_GREY) {  // "macroblock" = one 8x8 block
+    f->mbw = (uint32_t)w / 8;
+    f->nmb = f->mbw * ((uint32_t)h / 8);
+  } else {
+    f->mbw = (uint32_t)w / 16;
+    f->nmb = f->mbw * ((uint32_t)h / 16);
+  }
+  if ((uint64_t)f->nmb * fmt_blocks_per_mb(c->fmt) * 64 + kAllocPad >= 0xFFFFFFFFull)  // block offsets and the walkers' positions are 32-bit
     return fail(c, MI_RTJ_ERR_GEOMETRY, "picture of %dx%d: its worst-case stream does not fit 32-bit offsets", w, h);
   f->nchunks = (f->data_len + kChunk - 1) / kChunk;
   if (f->nchunks == 0) f->nchunks = 1;
   return MI_RTJ_OK;
+}
+
+// blocks, macroblock groups and plane bytes of a picture in the plan's format
+inline uint64_t frame_blocks(const FrameDev& f, int fmt) { return (uint64_t)f.nmb * fmt_blocks_per_mb(fmt); }
+inline uint32_t frame_groups(const FrameDev& f, int fmt) {
+  return (f.nmb + fmt_units_per_group(fmt) - 1u) / fmt_units_per_group(fmt);
+}
+inline size_t frame_plane_bytes(const FrameDev& f, int fmt) {
+  const size_t ysz = (size_t)f.w * f.h;
+  return fmt == MI_RTJ_FMT_YUV422 ? 2 * ysz : fmt == MI_RTJ_FMT_GREY ? ysz : ysz * 3 / 2;
 }
 
 // per-chunk scratch of a plan (re)sized for its frames; chunk_base / sum_base are set here
@@ -453,6 +483,46 @@ int plan_upload(mi_rtj_plan* p) {
   return MI_RTJ_OK;
 }
 
+// A 4:2:2 or greyscale plan: two kernels back to back on the instance's stream (rtj_format_kernels.h) — the serial index,
+// a wave per packet (MI_RTJ_K_EMIT), then the transform (MI_RTJ_K_DECODE).  No speculative or chunk-parallel index, no
+// second stream, no runs.
+int plan_launch_fmt(mi_rtj_plan* p, const uint8_t* st, uint8_t* out) {
+  mi_rtj_ctx* c = p->ctx;
+  hipStream_t const ds = c->stream;
+  c->input_dirty = false;  // (everything runs on the instance's stream)
+  Timed ti, td;
+  if (p->profile) {
+    HIPCHK(c, hipEventCreate(&ti.a));
+    HIPCHK(c, hipEventRecord(ti.a, ds));
+  }
+  const dim3 igrid(std::min<unsigned>((unsigned)p->n, 16384u)), block(kDecThreads);
+  const dim3 dgrid(fmt_parts(p->fmt) * p->max_groups, (unsigned)p->n);
+  if (p->fmt == MI_RTJ_FMT_YUV422)
+    hipLaunchKernelGGL(k_index_fmt<kFmtYUV422>, igrid, dim3(64), 0, ds, p->d_frames, (uint32_t)p->n, st, c->d_lut, p->d_blkoff);
+  else
+    hipLaunchKernelGGL(k_index_fmt<kFmtGrey>, igrid, dim3(64), 0, ds, p->d_frames, (uint32_t)p->n, st, c->d_lut, p->d_blkoff);
+  if (p->profile) {
+    HIPCHK(c, hipEventCreate(&ti.b));
+    HIPCHK(c, hipEventRecord(ti.b, ds));
+    p->ev[MI_RTJ_K_EMIT].push_back(ti);
+    td.a = ti.b;
+    td.owns_a = false;
+  }
+  if (p->fmt == MI_RTJ_FMT_YUV422)
+    hipLaunchKernelGGL(k_decode_fmt<kFmtYUV422>, dgrid, block, 0, ds, p->d_frames, st, c->d_lut, p->d_blkoff, out);
+  else
+    hipLaunchKernelGGL(k_decode_fmt<kFmtGrey>, dgrid, block, 0, ds, p->d_frames, st, c->d_lut, p->d_blkoff, out);
+  if (p->profile) {
+    HIPCHK(c, hipEventCreate(&td.b));
+    HIPCHK(c, hipEventRecord(td.b, ds));
+    p->ev[MI_RTJ_K_DECODE].push_back(td);
+  }
+  HIPCHK(c, hipGetLastError());
+  p->last = 0;
+  p->launches++;
+  return MI_RTJ_OK;
+}
+
 // what: the index kernels (kLaunchIndex), k_decode (kLaunchDecode) or both.  A session whose packets are indexed in
 // groups queues the index of a group once and then k_decode packet by packet (dframe = the packet's place in the group,
 // dcount = 1, d_out = its picture): a packet's unchanged blocks come from its predecessor's picture, so the pictures of
@@ -462,6 +532,7 @@ int plan_launch(mi_rtj_plan* p, const void* d_stream, void* d_out, int what = kL
                 int dcount = -1) {
   mi_rtj_ctx* c = p->ctx;
   const uint8_t* st = (const uint8_t*)d_stream;
+  if (p->fmt != MI_RTJ_FMT_YUV420) return plan_launch_fmt(p, st, (uint8_t*)d_out);
   // The index kernels run on `is`, k_decode on the instance's stream.  Plans have them equal; a session gives its slots
   // an index stream of their own (p->idx_stream), so that the index of packet i + 1 is built while packet i — whose
   // picture the unchanged blocks of i + 1 come from — is still being transformed.
@@ -825,6 +896,19 @@ const char* mi_rtj_last_error(const mi_rtj_ctx* c) {
   return copy.c_str();
 }
 
+int mi_rtj_set_format(mi_rtj_ctx* c, int fmt) {
+  if (!c) return MI_RTJ_ERR_ARG;
+  if (fmt != MI_RTJ_FMT_YUV420 && fmt != MI_RTJ_FMT_YUV422 && fmt != MI_RTJ_FMT_GREY)
+    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_set_format: unknown format %d (0 = 4:2:0, 1 = 4:2:2, 2 = greyscale)", fmt);
+  if (c->fmt_fixed && fmt != c->fmt)
+    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_set_format: the instance has decoded, planned or opened a session in format %d; "
+                "its persistent picture has that layout (make a new instance for format %d)", c->fmt, fmt);
+  c->fmt = fmt;
+  return MI_RTJ_OK;
+}
+
+int mi_rtj_get_format(const mi_rtj_ctx* c) { return c ? c->fmt : MI_RTJ_ERR_ARG; }
+
 void mi_rtj_get_state(const mi_rtj_ctx* c, int* w, int* h, int* q) {
   if (!c) return;
   if (w) *w = c->width;
@@ -897,6 +981,7 @@ mi_rtj_plan* mi_rtj_plan_create(mi_rtj_ctx* c, int n, const uint8_t* headers, co
   mi_rtj_plan* p = new mi_rtj_plan();
   p->ctx = c;
   p->n = n;
+  p->fmt = c->fmt;
   p->h_frames.resize(n);
   uint64_t blk_base = 0;
   for (int i = 0; i < n; i++) {
@@ -911,12 +996,12 @@ mi_rtj_plan* mi_rtj_plan_create(mi_rtj_ctx* c, int n, const uint8_t* headers, co
       return nullptr;
     }
     const FrameDev& f = p->h_frames[i];
-    const uint64_t nblk = (uint64_t)f.nmb * 6;
+    const uint64_t nblk = frame_blocks(f, p->fmt);
     p->n_blocks += nblk;
     blk_base += (nblk + 1 + 63) & ~63ull;  // keep every frame's index 256-byte aligned
     p->bytes_in += pkt_len[i];
-    p->bytes_out += (uint64_t)f.w * f.h * 3 / 2;
-    const uint32_t groups = (f.nmb + kMbPerGroup - 1) / kMbPerGroup;
+    p->bytes_out += frame_plane_bytes(f, p->fmt);
+    const uint32_t groups = frame_groups(f, p->fmt);
     if (groups > p->max_groups) p->max_groups = groups;
   }
   p->n_index = blk_base;
@@ -936,7 +1021,8 @@ mi_rtj_plan* mi_rtj_plan_create(mi_rtj_ctx* c, int n, const uint8_t* headers, co
     const char* spl = getenv("MI_RTJ_SPLIT");
     p->split = spl ? (atoi(spl) != 0) : -1;
   }
-  if (hipSetDevice(c->device) != hipSuccess || plan_alloc_chunks(p) != MI_RTJ_OK) {
+  // (a 4:2:2 or greyscale plan has the serial index only: no chunk scratch, no speculation)
+  if (hipSetDevice(c->device) != hipSuccess || (p->fmt == MI_RTJ_FMT_YUV420 && plan_alloc_chunks(p) != MI_RTJ_OK)) {
     mi_rtj_plan_destroy(p);
     return nullptr;
   }
@@ -955,6 +1041,7 @@ hipMalloc((void**)&p->d_blkoff, sizeof(uint32_t) * p->n_index) != hipSuccess) {
     const uint64_t groups = (uint64_t)p->n * p->max_groups;
     p->overlap = ov ? atoi(ov) == 1 : groups >= (uint64_t)kDecRotateMinGroups && groups < (uint64_t)kOverlapMaxGroups;
     p->overlap_dyn = ov ? atoi(ov) == 2 : !p->overlap && groups >= (uint64_t)kOverlapMaxGroups;  // (2: tests, on small plans)
+    if (p->fmt != MI_RTJ_FMT_YUV420) p->overlap = p->overlap_dyn = false;  // both kernels on the instance's stream
     if (p->overlap) {
       if (hipMalloc((void**)&p->d_blkoff_b, sizeof(uint32_t) * p->n_index) != hipSuccess ||
           hipStreamCreateWithFlags(&p->own_idx, hipStreamNonBlocking) != hipSuccess) {
@@ -983,6 +1070,7 @@ hipMalloc((void**)&p->d_blkoff, sizeof(uint32_t) * p->n_index) != hipSuccess) {
     mi_rtj_plan_destroy(p);
     return nullptr;
   }
+  c->fmt_fixed = true;
   return p;
 }
 
@@ -1171,7 +1259,7 @@ int mi_rtj_plan_read_index(mi_rtj_plan* p, uint32_t* dst, size_t max_entries) {
   size_t k = 0;
   for (int i = 0; i < p->n; i++) {
     const FrameDev& f = p->h_frames[i];
-    const size_t cnt = (size_t)f.nmb * 6 + 1;
+    const size_t cnt = (size_t)frame_blocks(f, p->fmt) + 1;
     if (k + cnt > max_entries) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_read_index: destination too small");
     memcpy(dst + k, all.data() + f.blk_base, cnt * sizeof(uint32_t));
     k += cnt;
@@ -1199,6 +1287,9 @@ int mi_rtj_plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len) {
   if (!p) return MI_RTJ_ERR_ARG;
   mi_rtj_ctx* c = p->ctx;
   if (n_runs < 0 || (n_runs > 0 && !run_len)) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: bad argument");
+  if (p->fmt != MI_RTJ_FMT_YUV420)
+    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: runs are for 4:2:0 plans; this plan's format is %s",
+                p->fmt == MI_RTJ_FMT_YUV422 ? "4:2:2" : "greyscale");
   // ---- check everything before anything changes: a refused call leaves the plan as it was ----
   std::vector<RunDev> runs;
   std::vector<RunChunkDev> chunks;
@@ -1339,10 +1430,12 @@ int decode_one_launch(mi_rtj_ctx* c, const uint8_t* pkt, size_t len) {
     c->single->spec_mode = sp ? atoi(sp) : -1;
   }
   mi_rtj_plan* p = c->single;
+  p->fmt = c->fmt;
   const int rc = fill_frame(c, pkt, 0, (uint32_t)len, 0, 0, &p->h_frames[0]);
   if (rc != MI_RTJ_OK) return rc;
+  c->fmt_fixed = true;
   const FrameDev& f = p->h_frames[0];
-  const size_t need_frame = (size_t)f.w * f.h * 3 / 2;
+  const size_t need_frame = frame_plane_bytes(f, p->fmt);
   if (need_frame > c->frame_bytes) {  // gavl_video_frame_create in init_rtjpeg (lib/video_rtjpeg.c:54)
     uint8_t* nf = nullptr;
     HIPCHK(c, hipMalloc((void**)&nf, need_frame + kAllocPad));
@@ -1363,7 +1456,7 @@ int decode_one_launch(mi_rtj_ctx* c, const uint8_t* pkt, size_t len) {
     c->pkt_cap = (len + kAllocPad) * 2;
     HIPCHK(c, hipMalloc((void**)&c->d_pkt, c->pkt_cap));
   }
-  const uint64_t nidx = (((uint64_t)f.nmb * 6 + 1) + 63) & ~63ull;
+  const uint64_t nidx = ((frame_blocks(f, p->fmt) + 1) + 63) & ~63ull;
   if (nidx > p->n_index) {
     if (p->d_blkoff) {
       HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1373,9 +1466,9 @@ int decode_one_launch(mi_rtj_ctx* c, const uint8_t* pkt, size_t len) {
     HIPCHK(c, hipMalloc((void**)&p->d_blkoff, sizeof(uint32_t) * nidx));
     p->n_index = nidx;
   }
-  p->n_blocks = (uint64_t)f.nmb * 6;
-  p->max_groups = (f.nmb + kMbPerGroup - 1) / kMbPerGroup;
-  {
+  p->n_blocks = frame_blocks(f, p->fmt);
+  p->max_groups = frame_groups(f, p->fmt);
+  if (p->fmt == MI_RTJ_FMT_YUV420) {
     const int rc2 = plan_alloc_chunks(p);  // lays the packet's chunks out; allocates only when it is larger than any before it
     if (rc2 != MI_RTJ_OK) return rc2;
   }
@@ -1397,14 +1490,19 @@ int mi_rtj_decode(mi_rtj_ctx* c, const uint8_t* pkt, size_t len, uint8_t* const 
   if (dst) {
     // gavl_video_frame_copy(format, f, priv->frame) (lib/video_rtjpeg.c:82): image_width x
     // image_height region, each side's own strides — done by the copy engine on the way out.
-    if (!dst[0] || !dst[1] || !dst[2] || !dst_stride) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_decode: NULL plane");
+    const bool grey = c->fmt == MI_RTJ_FMT_GREY;  // one plane: dst[1], dst[2] and their strides are not looked at
+    if (!dst[0] || (!grey && (!dst[1] || !dst[2])) || !dst_stride) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_decode: NULL plane");
     if (crop_w <= 0 || crop_h <= 0 || crop_w > (int)f.w || crop_h > (int)f.h)
       return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_decode: crop %dx%d outside the coded %ux%u picture", crop_w, crop_h, f.w, f.h);
     const size_t ysz = (size_t)f.w * f.h;
-    const int cw = (crop_w + 1) / 2, ch = (crop_h + 1) / 2;
+    // chroma: half the width; half the height too in 4:2:0, every line in 4:2:2
+    const size_t csz = c->fmt == MI_RTJ_FMT_YUV422 ? ysz / 2 : ysz / 4;
+    const int cw = (crop_w + 1) / 2, ch = c->fmt == MI_RTJ_FMT_YUV422 ? crop_h : (crop_h + 1) / 2;
     HIPCHK(c, hipMemcpy2DAsync(dst[0], (size_t)dst_stride[0], c->d_frame, f.w, (size_t)crop_w, (size_t)crop_h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpy2DAsync(dst[1], (size_t)dst_stride[1], c->d_frame + ysz, f.w / 2, (size_t)cw, (size_t)ch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpy2DAsync(dst[2], (size_t)dst_stride[2], c->d_frame + ysz + ysz / 4, f.w / 2, (size_t)cw, (size_t)ch, hipMemcpyDeviceToHost, c->stream));
+    if (!grey) {
+      HIPCHK(c, hipMemcpy2DAsync(dst[1], (size_t)dst_stride[1], c->d_frame + ysz, f.w / 2, (size_t)cw, (size_t)ch, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpy2DAsync(dst[2], (size_t)dst_stride[2], c->d_frame + ysz + csz, f.w / 2, (size_t)cw, (size_t)ch, hipMemcpyDeviceToHost, c->stream));
+    }
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return MI_RTJ_OK;
@@ -1415,7 +1513,7 @@ int mi_rtj_decode_nocopy(mi_rtj_ctx* c, const uint8_t* pkt, size_t len, const ui
   const int r = decode_one_launch(c, pkt, len);
   if (r != MI_RTJ_OK) return r;
   const FrameDev& f = c->single->h_frames[0];
-  const size_t ysz = (size_t)f.w * f.h, fsz = ysz * 3 / 2;
+  const size_t ysz = (size_t)f.w * f.h, fsz = frame_plane_bytes(f, c->fmt);
   if (fsz > c->h_frame_cap) {
     if (c->h_frame) (void)hipHostFree(c->h_frame);
     c->h_frame = nullptr;
@@ -1425,9 +1523,14 @@ int mi_rtj_decode_nocopy(mi_rtj_ctx* c, const uint8_t* pkt, size_t len, const ui
   HIPCHK(c, hipMemcpyAsync(c->h_frame, c->d_frame, fsz, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   planes[0] = c->h_frame;
-  planes[1] = c->h_frame + ysz;
-  planes[2] = c->h_frame + ysz + ysz / 4;
   strides[0] = (int)f.w;
+  if (c->fmt == MI_RTJ_FMT_GREY) {
+    planes[1] = planes[2] = nullptr;
+    strides[1] = strides[2] = 0;
+    return MI_RTJ_OK;
+  }
+  planes[1] = c->h_frame + ysz;
+  planes[2] = c->h_frame + ysz + (c->fmt == MI_RTJ_FMT_YUV422 ? ysz / 2 : ysz / 4);
   strides[1] = strides[2] = (int)f.w / 2;
   return MI_RTJ_OK;
 }
@@ -1642,10 +1745,16 @@ mi_rtj_pipe* mi_rtj_pipe_create(mi_rtj_ctx* c, int depth, int max_w, int max_h) 
     fail(c, MI_RTJ_ERR_ARG, "mi_rtj_pipe_create: bad argument (depth 2..64)");
     return nullptr;
   }
+  if (c->fmt != MI_RTJ_FMT_YUV420) {
+    fail(c, MI_RTJ_ERR_ARG, "mi_rtj_pipe_create: sessions decode 4:2:0 streams only; this instance's format is %s",
+         c->fmt == MI_RTJ_FMT_YUV422 ? "4:2:2 (MI_RTJ_FMT_YUV422)" : "greyscale (MI_RTJ_FMT_GREY)");
+    return nullptr;
+  }
   if (hipSetDevice(c->device) != hipSuccess) {
     fail(c, MI_RTJ_ERR_HIP, "mi_rtj_pipe_create: hipSetDevice failed");
     return nullptr;
   }
+  c->fmt_fixed = true;
   mi_rtj_pipe* q = new mi_rtj_pipe();
   q->ctx = c;
   q->depth = depth;
@@ -2245,6 +2354,22 @@ int mi_rtj_yuv420_to_rgb(mi_rtj_ctx* c, int fmt, int w, int h, int n, const void
     case kFmtBGR24: hipLaunchKernelGGL(k_yuv420_to_rgb<kFmtBGR24>, grid, block, 0, c->stream, in, in_frame_stride, out, row_pitch, out_frame_stride, w, h); break;
     default:        hipLaunchKernelGGL(k_yuv420_to_rgb<kFmtRGB16>, grid, block, 0, c->stream, in, in_frame_stride, out, row_pitch, out_frame_stride, w, h); break;
   }
+  HIPCHK(c, hipGetLastError());
+  return MI_RTJ_OK;
+}
+
+int mi_rtj_yuv422_to_rgb24(mi_rtj_ctx* c, int w, int h, int n, const void* d_planes, size_t in_frame_stride, void* d_rgb,
+                           size_t row_pitch, size_t out_frame_stride) {
+  if (!c || !d_planes || !d_rgb || w <= 0 || h <= 0 || (w & 15) || (h & 7) || n <= 0 || n > kMaxPlanFrames)
+    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_yuv422_to_rgb24: bad argument");
+  if (row_pitch < (size_t)w * 3 || (row_pitch & 15) || ((uintptr_t)d_rgb & 15) || (out_frame_stride & 15) ||
+      (in_frame_stride & 15) || ((uintptr_t)d_planes & 15))
+    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_yuv422_to_rgb24: buffers, row pitch and frame strides must be 16-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  const long long tiles = (long long)(w / 8) * h;
+  const dim3 grid((unsigned)((tiles + 255) / 256 < 2048 ? (tiles + 255) / 256 : 2048), (unsigned)n), block(256);
+  hipLaunchKernelGGL(k_yuv422_rgb24, grid, block, 0, c->stream, (const uint8_t*)d_planes, in_frame_stride, (uint8_t*)d_rgb,
+                     row_pitch, out_frame_stride, w, h);
   HIPCHK(c, hipGetLastError());
   return MI_RTJ_OK;
 }

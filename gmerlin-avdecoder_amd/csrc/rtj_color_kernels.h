@@ -99,6 +99,42 @@ __global__ __launch_bounds__(256) void k_yuv420_to_rgb(const uint8_t* __restrict
   }
 }
 
+// YUV 4:2:2 -> RGB24: RTjpeg_yuv422rgb24 (lib/RTjpeg.c:3077-3121; constants :3071-3075).  Planes as the 4:2:2 decoder
+// writes them: Y w x h, then Cb and Cr, w/2 x h each — one Cb/Cr pair per two pixels of EVERY row.  Each thread converts
+// an 8x1 pixel tile (one 8-byte luma load, one 4-byte load per chroma plane) and writes 24 bytes; the bytes of a row
+// behind its 3 w are not touched.
+__global__ __launch_bounds__(256) void k_yuv422_rgb24(const uint8_t* __restrict__ planes, size_t in_frame_stride,
+                                                       uint8_t* __restrict__ rgb, size_t row_pitch,
+                                                       size_t out_frame_stride, int w, int h) {
+  const uint8_t* f = planes + (size_t)blockIdx.y * in_frame_stride;
+  uint8_t* o = rgb + (size_t)blockIdx.y * out_frame_stride;
+  const int tiles_x = w >> 3, tiles = tiles_x * h;
+  const size_t ysz = (size_t)w * h;
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < tiles; t += gridDim.x * blockDim.x) {
+    const int ty = t / tiles_x, tx = t - ty * tiles_x;
+    const uint2 y8 = *(const uint2*)(f + (size_t)ty * w + 8 * tx);
+    const uint32_t cb4 = *(const uint32_t*)(f + ysz + (size_t)ty * (w >> 1) + 4 * tx);
+    const uint32_t cr4 = *(const uint32_t*)(f + ysz + (ysz >> 1) + (size_t)ty * (w >> 1) + 4 * tx);
+    uint32_t wd[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const int yv = ((i < 4 ? y8.x : y8.y) >> (8 * (i & 3))) & 0xFF;
+      const int cb = (cb4 >> (8 * (i >> 1))) & 0xFF, cr = (cr4 >> (8 * (i >> 1))) & 0xFF;
+      const Rgb p = yuv2rgb(yv, cb, cr);
+      const uint32_t c[3] = {(uint32_t)p.r, (uint32_t)p.g, (uint32_t)p.b};
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const int byte = 3 * i + k;
+        wd[byte >> 2] |= c[k] << (8 * (byte & 3));
+      }
+    }
+    uint2* d2 = (uint2*)(o + (size_t)ty * row_pitch + 24 * tx);
+    d2[0] = make_uint2(wd[0], wd[1]);
+    d2[1] = make_uint2(wd[2], wd[3]);
+    d2[2] = make_uint2(wd[4], wd[5]);
+  }
+}
+
 // plain streaming copy, 16 bytes per lane: the yardstick for what a pure HBM-bound kernel sustains
 __global__ __launch_bounds__(256) void k_copy16(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = src[i];

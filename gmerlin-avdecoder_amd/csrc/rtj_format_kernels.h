@@ -1,0 +1,343 @@
+// rtj_format_kernels.h — gfx950 kernels of the two other arms of RTjpeg_decompress (lib/RTjpeg.c:3580-3585):
+//
+//   RTjpeg_decompressYUV422 (lib/RTjpeg.c:2639-2686)  macroblock = 16x8 pixels: Y, Y, Cb, Cr; chroma planes w/2 x h
+//   RTjpeg_decompress8      (lib/RTjpeg.c:2751-2772)  8x8 luma blocks in raster order, one plane
+//
+//   k_index_fmt<Fmt>    block-start index: walk_packet (rtj_decode_kernels.h) with the format's block pattern as a
+//                       compile-time list, one wave per packet, packets side by side (grid-stride).
+//   k_decode_fmt<Fmt>   dequantise + inverse transform + plane scatter, one lane per 8x8 block, one wave per part of a
+//                       group.  The arithmetic is the 4:2:0 path's: the packed passes of rtj_idct_pk.h behind their
+//                       per-block range test, the one-value-per-register passes of rtj_idct_asm.h as the fallback,
+//                       transform_lo for waves whose blocks stay inside the low 4x4, px() for the clamp.
+//
+// The descriptors are the 4:2:0 path's (FrameDev), read per format:
+//   4:2:2  mbw = w / 16, nmb = mbw * (h / 8), 4 blocks per macroblock
+//   grey   mbw = w / 8,  nmb = mbw * (h / 8), 1 block per "macroblock"
+// Nothing here is called by the 4:2:0 kernels and nothing of theirs is changed.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "rtj_common.h"
+#include "rtj_decode_kernels.h"
+
+namespace mirtj {
+
+enum { kFmtYUV420 = 0, kFmtYUV422 = 1, kFmtGrey = 2 };
+
+template <int Fmt>
+struct FmtShape;
+template <>
+struct FmtShape<kFmtYUV422> {
+  static constexpr uint32_t kBlkPerMb = 4;  // Y Y Cb Cr
+  static constexpr uint32_t kParts = 2;     // of a group of kMbPerGroup macroblocks: 64 luma blocks | 32 Cb + 32 Cr
+  static constexpr uint32_t kUnitsPerGroup = (uint32_t)kMbPerGroup;
+};
+template <>
+struct FmtShape<kFmtGrey> {
+  static constexpr uint32_t kBlkPerMb = 1;
+  static constexpr uint32_t kParts = 1;  // a group is 64 consecutive blocks in raster order
+  static constexpr uint32_t kUnitsPerGroup = 64;
+};
+
+__host__ __device__ constexpr uint32_t fmt_blocks_per_mb(int fmt) { return fmt == kFmtYUV422 ? 4u : fmt == kFmtGrey ? 1u : 6u; }
+__host__ __device__ constexpr uint32_t fmt_units_per_group(int fmt) { return fmt == kFmtGrey ? 64u : (uint32_t)kMbPerGroup; }
+__host__ __device__ constexpr uint32_t fmt_parts(int fmt) { return fmt == kFmtYUV422 ? 2u : fmt == kFmtGrey ? 1u : 3u; }
+
+// ---------------------------------------------------------------------------------------
+// walk_packet_fmt: walk_packet (rtj_decode_kernels.h:214-294) for the format's macroblock.  One wave, the position in
+// scalar registers, both windows searched at once, one straight path per block; the macroblock's blocks are unrolled
+// from the compile-time pattern, so a block's raw-byte count is a loop constant.  The host refuses tables with more
+// than kMaxRawBytes raw coefficients, so a block always ends behind a byte of the two windows.
+// Bounds no stream reaches: a block is at most 64 bytes, so its successor starts at most 128 bytes behind the window's
+// base (63 + 64 + 1) and the window slides at most twice per block; the macroblock loop runs f.nmb times.
+// ---------------------------------------------------------------------------------------
+template <int Fmt>
+__device__ __forceinline__ void walk_packet_fmt(const FrameDev& f, const uint8_t* __restrict__ stream,
+                                                const QTab* __restrict__ lut, uint32_t* __restrict__ out) {
+  constexpr uint32_t kB = FmtShape<Fmt>::kBlkPerMb;
+  const uint32_t lane = threadIdx.x & 63u;
+  const __amdgpu_buffer_rsrc_t rs =
+      __builtin_amdgcn_make_buffer_rsrc((void*)(stream + f.data_off), 0, (int)f.data_len, 0x00020000);
+  // a stream byte as int8; the descriptor returns 0 at or past the packet's end
+  auto fetch = [&](uint32_t pos) -> int {
+    return (int)(int8_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(pos + lane), 0, 0);
+  };
+  auto weight = [](int b) -> uint32_t {  // token_weight() of an int8
+    const int x = b - 63;
+    return (uint32_t)(x < 1 ? 1 : x > 64 ? 64 : x);
+  };
+  const uint32_t lb8 = (uint32_t)lut[f.qidx].lb8, cb8 = (uint32_t)lut[f.qidx].cb8;
+  const uint32_t need_l = 63u - lb8, need_c = 63u - cb8;
+  uint32_t base = 0, Wc, Wn;
+  int pf1, pf2, pf3;
+  unsigned long long ffc, ffn;  // lanes of the two windows that hold 0xFF
+  {
+    const int cur = fetch(0u), nxt = fetch(64u);
+    pf1 = fetch(128u);
+    pf2 = fetch(192u);
+    pf3 = fetch(256u);
+    Wc = wave_incl_scan(weight(cur));
+    Wn = wave_incl_scan(weight(nxt)) + (uint32_t)__builtin_amdgcn_readlane((int)Wc, 63);
+    ffc = __ballot(cur == -1);
+    ffn = __ballot(nxt == -1);
+  }
+  uint32_t lp = 0;  // the current block's start, relative to base
+  uint32_t j = 0;   // offsets gathered in acc since the last store
+  uint32_t acc = 0;
+  uint32_t* o = out;  // where acc's lane 0 goes
+  auto flush = [&]() {
+    if (lane < j) o[lane] = acc;
+    o += j;
+    j = 0;
+  };
+  auto step = [&](const uint32_t bt8, const uint32_t need, const int c) {  // c: the block's number in its macroblock
+    for (int s = 0; s < 2 && lp >= 64u; s++) {  // slide the two windows forward (lp <= 128: twice at the most)
+      base += 64u;
+      lp -= 64u;
+      const int b = pf1;
+      pf1 = pf2;
+      pf2 = pf3;
+      pf3 = fetch(base + 256u);
+      Wc = Wn;
+      ffc = ffn;
+      Wn = wave_incl_scan(weight(b)) + (uint32_t)__builtin_amdgcn_readlane((int)Wc, 63);
+      ffn = __ballot(b == -1);
+    }
+    asm("s_add_i32 m0, %2, %3\n\tv_writelane_b32 %0, %1, m0" : "+v"(acc) : "s"(base + lp), "s"(j), "n"(c) : "m0", "scc");
+    const uint32_t iq = lp + bt8;  // last non-token byte of the block, 0..78
+    const uint32_t wq_c = (uint32_t)__builtin_amdgcn_readlane((int)Wc, (int)(iq & 63u));
+    const uint32_t wq_n = (uint32_t)__builtin_amdgcn_readlane((int)Wn, (int)(iq & 63u));
+    const uint32_t target = (iq < 64u ? wq_c : wq_n) + need;
+    const unsigned long long mc = __ballot(Wc >= target), mn = __ballot(Wn >= target);
+    uint32_t ec, en;
+    asm("s_ff1_i32_b64 %0, %1" : "=s"(ec) : "s"(mc));
+    asm("s_ff1_i32_b64 %0, %1" : "=s"(en) : "s"(mn));
+    en |= 64u;
+    const uint32_t e = ec < en ? ec : en;
+    asm("s_bitcmp1_b64 %1, %2\n\ts_cselect_b32 %0, %3, %4" : "=s"(lp) : "s"(ffc), "s"(lp), "s"(lp + 1u), "s"(e + 1u) : "scc");
+  };
+  for (uint32_t mb = 0; mb < f.nmb; ++mb) {
+    if (j > 64u - kB) flush();
+    if (Fmt == kFmtYUV422) {
+      step(lb8, need_l, 0);
+      step(lb8, need_l, 1);
+      step(cb8, need_c, 2);
+      step(cb8, need_c, 3);
+    } else {
+      step(lb8, need_l, 0);
+    }
+    j += kB;
+  }
+  if (j > 63u) flush();
+  asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(acc) : "s"(base + lp), "s"(j) : "m0");  // the end
+  j += 1u;
+  flush();
+}
+
+// The packets of a plan, a wave each, side by side (grid-stride over the packets as in k_index_walk_todo).
+template <int Fmt>
+__global__ __launch_bounds__(64) void k_index_fmt(const FrameDev* __restrict__ frames, uint32_t nframes,
+                                                   const uint8_t* __restrict__ stream, const QTab* __restrict__ lut,
+                                                   uint32_t* __restrict__ blkoff) {
+  for (uint32_t i = blockIdx.x; i < nframes; i += gridDim.x) {
+    const FrameDev f = frames[i];
+    walk_packet_fmt<Fmt>(f, stream, lut, blkoff + f.blk_base);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// k_decode_fmt<Fmt>: grid (parts * groups, frames), one wave per workgroup and part of a group.
+//   4:2:2  group = kMbPerGroup consecutive macroblocks.  part 0: their 64 luma blocks — lane l has block l & 1 of
+//          macroblock l >> 1, so the wave's row stores cover 512 contiguous pixels of one 8-line row (or two or more
+//          stretches where the group wraps a picture row); part 1: lanes 0-31 the Cb blocks, lanes 32-63 the Cr blocks:
+//          2 x 256 contiguous bytes.
+//   grey   group = 64 consecutive blocks in raster order: 512 contiguous pixels.
+// Lanes past the picture's last block have nothing to do (the partial last group).
+// A lane reads its block's bytes 16 at a time through a buffer descriptor that returns 0 at or past the packet's end
+// (RTjpeg_s2b's length rule, lib/RTjpeg.c:157-186: at most 64 bytes, four rounds), dequantises into its LDS scratch in
+// the column-pair layout of coef_byte(), and runs the transform in registers.  A block whose first byte is 0xFF leaves
+// its 8x8 destination as it was (lib/RTjpeg.c:2654, 2764).
+// ---------------------------------------------------------------------------------------
+constexpr int kFmtLdsWords = kCoefWords + 64;  // the lanes' coefficient scratch, then the part's slot table
+
+template <int Fmt>
+__global__ __launch_bounds__(kDecThreads) void k_decode_fmt(const FrameDev* __restrict__ frames,
+                                                            const uint8_t* __restrict__ stream,
+                                                            const QTab* __restrict__ lut,
+                                                            const uint32_t* __restrict__ blkoff,
+                                                            uint8_t* __restrict__ outbuf) {
+  using S = FmtShape<Fmt>;
+  __shared__ __attribute__((aligned(16))) uint32_t s_lds[kFmtLdsWords];
+  uint32_t* s_tab = s_lds + kCoefWords;
+  const FrameDev f = frames[blockIdx.y];
+  const uint32_t grp = blockIdx.x / S::kParts, part = blockIdx.x - grp * S::kParts;  // wave-uniform
+  const uint32_t ngroups = (f.nmb + S::kUnitsPerGroup - 1u) / S::kUnitsPerGroup;
+  if (grp >= ngroups) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool chroma = Fmt == kFmtYUV422 && part == 1u;
+  const QTab& qt = lut[f.qidx];
+  const uint32_t bt8 = (uint32_t)(chroma ? qt.cb8 : qt.lb8);
+  {  // slot k of the zig-zag order: dequantiser << 16 | byte offset in the lane's scratch
+    const int nat = c_zz[lane];
+    s_tab[lane] = ((uint32_t)(chroma ? qt.ciqt[nat] : qt.liqt[nat]) << 16) | (uint32_t)coef_byte(nat);
+  }
+  wave_lds_sync();
+
+  // ---- which block this lane has and where its eight rows go ----
+  uint32_t unit, kblk;  // macroblock (grey: block) of the picture, block of the macroblock
+  if (Fmt == kFmtYUV422) {
+    unit = grp * S::kUnitsPerGroup + (chroma ? (lane & 31u) : (lane >> 1));
+    kblk = chroma ? 2u + (lane >> 5) : (lane & 1u);
+  } else {
+    unit = grp * S::kUnitsPerGroup + lane;
+    kblk = 0u;
+  }
+  const bool valid = unit < f.nmb;
+  const uint32_t uy = unit / f.mbw, ux = unit - uy * f.mbw;
+  const size_t ysz = (size_t)f.w * f.h;
+  uint32_t stride;
+  size_t dst_off;
+  if (Fmt == kFmtYUV422 && chroma) {
+    stride = f.w >> 1;
+    dst_off = ysz + (kblk == 3u ? ysz >> 1 : (size_t)0) + (size_t)(8u * uy) * stride + 8u * ux;
+  } else if (Fmt == kFmtYUV422) {
+    stride = f.w;
+    dst_off = (size_t)(8u * uy) * stride + 16u * ux + 8u * kblk;
+  } else {
+    stride = f.w;
+    dst_off = (size_t)(8u * uy) * stride + 8u * ux;
+  }
+  uint8_t* dst = outbuf + f.out_off + dst_off;
+
+  const __amdgpu_buffer_rsrc_t rs =
+      __builtin_amdgcn_make_buffer_rsrc((void*)(stream + f.data_off), 0, (int)f.data_len, 0x00020000);
+  const uint32_t pos = valid ? blkoff[f.blk_base + S::kBlkPerMb * unit + kblk] : 0u;
+  auto byte_at = [&](uint32_t p) -> uint32_t { return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)p, 0, 0); };
+
+  const uint32_t my_a = lds_address(s_lds) + lane * (uint32_t)(kCoefStride * 2);
+  const uint4* my = (const uint4*)((const uint8_t*)s_lds + (size_t)lane * (kCoefStride * 2));
+  const uint32_t tab_a = lds_address(s_tab);
+
+  uint32_t bytes[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) bytes[i] = byte_at(pos + (uint32_t)i);
+  const bool live = valid && bytes[0] != 0xFFu;
+
+  if (live) {
+    {
+      uint4* z = (uint4*)my;
+#pragma unroll
+      for (int i = 0; i < 8; i++) z[i] = make_uint4(0, 0, 0, 0);
+    }
+    // ---- stream -> dequantised coefficients, int16 (lib/RTjpeg.c:157-186): slot 0 is the unsigned DC, slots 1..bt8
+    // signed raw bytes, then tokens: 64..127 a run of token - 63 zero slots, anything else one coefficient ----
+    uint32_t co = 0;
+    for (int round = 0; round < 4; round++) {  // 64 bytes: the longest block
+#pragma unroll
+      for (int i = 0; i < 16; i++) {
+        const uint32_t ub = bytes[i];
+        const int sb = (int)(int8_t)ub;
+        if (co < 64u) {
+          if (co <= bt8 || sb <= 63) {
+            const uint32_t e = *(const lds_u32_t*)(uintptr_t)(tab_a + 4u * co);
+            const int v = co == 0u ? (int)ub : sb;
+            *(lds_i16_t*)(uintptr_t)(my_a + (e & 0xFFFFu)) = (int16_t)mul24(v, (int)(e >> 16));  // |v| < 2^8, dequantiser < 2^14
+            co += 1u;
+          } else {
+            co += (uint32_t)(sb - 63);  // the scratch is zero already
+          }
+        }
+      }
+      if (co >= 64u || round == 3) break;
+#pragma unroll
+      for (int i = 0; i < 16; i++) bytes[i] = byte_at(pos + 16u * (uint32_t)(round + 1) + (uint32_t)i);
+    }
+  }
+
+  wave_lds_sync();  // the coefficient stores (int16) before the reads of whole column pairs below
+
+  // ---- does any block of the wave reach outside the low 4x4? ----
+  uint32_t hi = 0;
+  if (live) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      if (i == 0 || i == 2) continue;  // rows 0-3 of columns 0-3
+      const uint4 q = my[i];
+      hi |= q.x | q.y | q.z | q.w;
+    }
+  }
+  const bool lo = !__any(hi != 0u);
+
+  if (live) {
+    auto put_packed = [&](uint2 o) {  // one row of the block, already clamped and packed
+      typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+      u32x2_t ov;
+      ov.x = o.x;
+      ov.y = o.y;
+      __builtin_nontemporal_store(ov, (u32x2_t*)dst);
+      dst += stride;
+    };
+    const IdctK K{362, 473, -669, 277, 128, 235};
+    const IdctPK KP = idct_pk_constants();
+    if (lo) {
+      transform_lo(my, K, KP, put_packed);
+    } else {
+      uint4 q[8];
+#pragma unroll
+      for (int i = 0; i < 8; i++) q[i] = my[i];
+      const bool packed = __all(pk_range_full(q, KP));  // wave-uniform: every live block inside the 16-bit budget
+      if (packed) {
+        // ---- column pass on the four column pairs, as they lie in the scratch (rtj_idct_pk.h) ----
+        uint32_t yy[4][8];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          uint32_t x[8] = {q[2 * j].x,     q[2 * j].y,     q[2 * j].z,     q[2 * j].w,
+                           q[2 * j + 1].x, q[2 * j + 1].y, q[2 * j + 1].z, q[2 * j + 1].w};
+          if (j == 0) idct8_pk_col<true>(x, KP);
+          else idct8_pk_col<false>(x, KP);
+#pragma unroll
+          for (int r = 0; r < 8; r++) yy[j][r] = x[r];
+        }
+        // ---- row pass on the four row pairs + scatter ----
+#pragma unroll
+        for (int r = 0; r < 8; r += 2) {
+          uint2 o0, o1;
+          uint32_t ya[4] = {yy[0][r], yy[1][r], yy[2][r], yy[3][r]};
+          uint32_t yb[4] = {yy[0][r + 1], yy[1][r + 1], yy[2][r + 1], yy[3][r + 1]};
+          idct8_pk_row_px(ya, yb, o0, o1, KP);
+          put_packed(o0);
+          put_packed(o1);
+        }
+      } else {
+        // ---- the one-value-per-register passes, in two rounds (rows 0-3, rows 4-7) as in decode_wave: the scratch is
+        // read again through an address the compiler cannot tell from the one above, so that the range test's 32
+        // registers do not stay alive next to the column results ----
+        uint32_t again = lane * (uint32_t)(kCoefStride * 2);
+        asm volatile("" : "+v"(again));
+        const uint4* mq = (const uint4*)((const uint8_t*)s_lds + again);
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+          int ws[4][8];
+          int y[8];
+          idct8_col<true, false>(mq[0], mq[1], y, K);
+#pragma unroll
+          for (int r = 0; r < 4; r++) ws[r][0] = y[4 * half + r];
+#pragma unroll
+          for (int c = 1; c < 8; c++) {
+            if (c & 1) idct8_col<false, true>(mq[c - 1], mq[c], y, K);
+            else idct8_col<false, false>(mq[c], mq[c + 1], y, K);
+#pragma unroll
+            for (int r = 0; r < 4; r++) ws[r][c] = y[4 * half + r];
+          }
+#pragma unroll
+          for (int r = 0; r < 4; r++)
+            put_packed(idct8_row_px(ws[r][0], ws[r][1], ws[r][2], ws[r][3], ws[r][4], ws[r][5], ws[r][6], ws[r][7], K));
+          asm volatile("" : "+v"(again));
+          mq = (const uint4*)((const uint8_t*)s_lds + again);
+        }
+      }
+    }
+  }
+}
+
+}  // namespace mirtj

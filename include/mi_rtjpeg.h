@@ -29,7 +29,8 @@ enum {
   MI_RTJ_ERR_HIP = -2,       /* a HIP runtime call failed (text in mi_rtj_last_error) */
   MI_RTJ_ERR_ARG = -3,       /* NULL / out-of-range argument */
   MI_RTJ_ERR_GEOMETRY = -4,  /* header width/height not positive multiples of 16: the reference's
-                                macroblock loop (lib/RTjpeg.c:2701-2703) never terminates on these */
+                                macroblock loop (lib/RTjpeg.c:2701-2703) never terminates on these
+                                (4:2:2 and greyscale instances: see mi_rtj_set_format) */
   MI_RTJ_ERR_NOMEM = -5
 };
 
@@ -49,6 +50,24 @@ void mi_rtj_destroy(mi_rtj_ctx *ctx);
 /* Text of the last failure on this instance (ctx == NULL: last mi_rtj_create failure). */
 const char *mi_rtj_last_error(const mi_rtj_ctx *ctx);
 
+/* ---- picture format: the arm of RTjpeg_decompress's switch (lib/RTjpeg.c:3580-3585) ----
+ * replaces RTjpeg_set_format (lib/RTjpeg.c:2421; RTJ_YUV420 / RTJ_YUV422 / RTJ_RGB8, include/RTjpeg.h:111-113).
+ * An instance starts in 4:2:0.  The format can be set before the instance's first decode, plan or session; later only
+ * the format it already has is accepted (the persistent picture of the one-packet path has one layout).  Any other
+ * call, and an unknown format, returns MI_RTJ_ERR_ARG with a message and changes nothing.
+ *   MI_RTJ_FMT_YUV422  RTjpeg_decompressYUV422 (lib/RTjpeg.c:2639-2686).  Width a positive multiple of 16, height a
+ *                      positive multiple of 8 (else MI_RTJ_ERR_GEOMETRY: the loops of :2651-2653 would not end or would
+ *                      write outside the planes).  Planes: Y w x h, Cb and Cr w/2 x h each, contiguous, 2 w h bytes;
+ *                      blocks per 16x8 macroblock: Y, Y, Cb, Cr; chroma stride w/2.
+ *   MI_RTJ_FMT_GREY    RTjpeg_decompress8 (lib/RTjpeg.c:2751-2772).  Width and height positive multiples of 8.  One
+ *                      plane, w h bytes, blocks in raster order, all with the luma tables.
+ * Header state machine (size and quality changes), the all-zero tables of a fresh decoder whose first packet says
+ * quality 0, zero bytes past a packet's end and unchanged (0xFF) blocks are as in 4:2:0.
+ * The plugin wrapper (video_rtjpeg_mi355x.c) stays 4:2:0, as the reference's (lib/video_rtjpeg.c:52). */
+enum { MI_RTJ_FMT_YUV420 = 0, MI_RTJ_FMT_YUV422 = 1, MI_RTJ_FMT_GREY = 2 }; /* RTJ_YUV420 / RTJ_YUV422 / RTJ_RGB8 */
+int mi_rtj_set_format(mi_rtj_ctx *ctx, int fmt);
+int mi_rtj_get_format(const mi_rtj_ctx *ctx);
+
 /* ---- one packet in, one frame out ----
  * replaces RTjpeg_decompress(rtj, p->buf.buf, priv->frame->planes) followed by
  * gavl_video_frame_copy(format, f, priv->frame)  (lib/video_rtjpeg.c:81-83; lib/RTjpeg.c:3565-3586).
@@ -56,13 +75,16 @@ const char *mi_rtj_last_error(const mi_rtj_ctx *ctx);
  * 0xFF "unchanged" blocks (lib/RTjpeg.c:2704) keep the previous frame's pixels.
  * dst[0..2]/dst_stride[0..2] describe the caller's Y, U, V planes (gavl_video_frame_t planes[]/
  * strides[]); the crop_w x crop_h top-left region (image_width x image_height) is copied.
- * dst == NULL decodes into the persistent frame only.  Returns MI_RTJ_OK or an error. */
+ * dst == NULL decodes into the persistent frame only.  Returns MI_RTJ_OK or an error.
+ * 4:2:2 instances: the chroma planes are cropped to (crop_w + 1) / 2 x crop_h.  Greyscale instances: dst[1], dst[2] and
+ * their strides are ignored and may be NULL. */
 int mi_rtj_decode(mi_rtj_ctx *ctx, const uint8_t *pkt, size_t len, uint8_t *const dst[3],
                   const int dst_stride[3], int crop_w, int crop_h);
 /* The same decode for a decoder that owns its output frame (the reference's "nocopy" mode: the
  * decoder sets s->vframe in init and decode(s, NULL) leaves the picture there, lib/video.c:253-277,
  * 420-429).  The whole coded picture lands in pinned host memory owned by the instance; planes[]/
- * strides[] describe it (stride = coded width) and stay valid until the next decode call. */
+ * strides[] describe it (stride = coded width) and stay valid until the next decode call.
+ * Greyscale instances: planes[1] = planes[2] = NULL, strides[1] = strides[2] = 0. */
 int mi_rtj_decode_nocopy(mi_rtj_ctx *ctx, const uint8_t *pkt, size_t len, const uint8_t *planes[3],
                          int strides[3]);
 
@@ -84,7 +106,9 @@ int mi_rtj_decode_nocopy(mi_rtj_ctx *ctx, const uint8_t *pkt, size_t len, const 
  *                    says otherwise is refused before anything is allocated for it — the reference's frame has the
  *                    container's size whatever a packet claims (lib/video_rtjpeg.c:50-54)
  * One session per stream; not thread safe; the instance's header-driven state (mi_rtj_get_state) is shared with
- * the one-packet calls, which must not be mixed into a running session. */
+ * the one-packet calls, which must not be mixed into a running session.
+ * Sessions are 4:2:0 only: on a 4:2:2 or greyscale instance mi_rtj_pipe_create returns NULL and mi_rtj_last_error(ctx)
+ * names the format. */
 typedef struct mi_rtj_pipe mi_rtj_pipe;
 mi_rtj_pipe *mi_rtj_pipe_create(mi_rtj_ctx *ctx, int depth, int coded_w, int coded_h);
 void mi_rtj_pipe_destroy(mi_rtj_pipe *pipe);
@@ -127,7 +151,11 @@ int mi_rtj_sync(mi_rtj_ctx *ctx); /* wait for everything queued on the instance'
  * (Y at out_offset, then U, then V, contiguous, stride = width as lib/RTjpeg.c:2708,2741 write).
  * headers: n * 12 bytes (host).  pkt_offset/pkt_len: whole packets, header included.
  * Packets are independent pictures: an unchanged (0xFF) block leaves its output slot as it was.  For streams with
- * unchanged blocks, cut the plan into runs (mi_rtj_plan_set_runs below). */
+ * unchanged blocks, cut the plan into runs (mi_rtj_plan_set_runs below).
+ * A plan takes the instance's format (mi_rtj_set_format) when it is created; 4:2:2: Y, Cb, Cr contiguous, 2 w h bytes;
+ * greyscale: Y alone.  Such a plan is indexed by one wave per packet (MI_RTJ_K_EMIT) and transformed by one kernel
+ * (MI_RTJ_K_DECODE), both on the instance's stream: the speculative and the chunk-parallel index stay 4:2:0, so
+ * mi_rtj_plan_spec_stats says 0 walkers, mi_rtj_plan_decode_form -1 and mi_rtj_plan_overlapped 0. */
 mi_rtj_plan *mi_rtj_plan_create(mi_rtj_ctx *ctx, int n, const uint8_t *headers,
                                 const uint64_t *pkt_offset, const uint32_t *pkt_len,
                                 const uint64_t *out_offset);
@@ -140,7 +168,8 @@ void mi_rtj_plan_destroy(mi_rtj_plan *plan);
  * library queued on the instance's stream before the call (mi_rtj_dev_memset; mi_rtj_h2d and the encoder entry points
  * are synchronous).  A caller that writes d_stream with work of its own must finish it before calling. */
 int mi_rtj_plan_decode(mi_rtj_plan *plan, const void *d_stream, void *d_out);
-/* Frames in the plan, total blocks, total algorithmic bytes (packet bytes read + plane bytes written). */
+/* Frames in the plan, total blocks, total algorithmic bytes (packet bytes read + plane bytes written), each by the
+ * plan's format: 6 / 4 / 1 blocks per macroblock, 1.5 / 2 / 1 bytes per pixel. */
 void mi_rtj_plan_info(const mi_rtj_plan *plan, int *n_frames, uint64_t *n_blocks,
                       uint64_t *bytes_in, uint64_t *bytes_out);
 /* Per-kernel device time: when enabled, mi_rtj_plan_decode brackets each kernel with HIP events
@@ -200,7 +229,8 @@ int mi_rtj_plan_overlapped(const mi_rtj_plan *plan);
  * plan's packets, the packets of a run do not all have the same coded size after the plan's header logic (a size change
  * inside a run is refused), or the output pictures of a run overlap one another.  Every buffer the runs need (about
  * 10 bytes per block and 64 pictures of a run: 125 MB for 16,384 pictures of 1080p) is allocated here; launches allocate
- * and synchronise nothing.  Synchronises the instance's stream. */
+ * and synchronise nothing.  Synchronises the instance's stream.
+ * Runs are 4:2:0 only: on a 4:2:2 or greyscale plan the call returns MI_RTJ_ERR_ARG and leaves the plan as it was. */
 int mi_rtj_plan_set_runs(mi_rtj_plan *plan, int n_runs, const int *run_len);
 /* While profiling (mi_rtj_plan_profile): device time of the run kernels summed over the decodes since profiling was
  * switched on, *launches = decodes that ran them.  (mi_rtj_plan_times keeps its kernels; mi_rtj_plan_step_times ends
@@ -210,12 +240,13 @@ int mi_rtj_plan_run_times(mi_rtj_plan *plan, float *ms, int *launches);
  * kernels.  Synchronises the instance's stream. */
 int mi_rtj_plan_run_stats(mi_rtj_plan *plan, long long *copied);
 /* Test hook: copy the plan's block-start index (relative to each packet's first data byte,
- * nblocks+1 entries per frame, frames back to back) to the host after a decode. */
+ * nblocks+1 entries per frame by the plan's format, frames back to back) to the host after a decode. */
 int mi_rtj_plan_read_index(mi_rtj_plan *plan, uint32_t *dst, size_t max_entries);
 
 /* ---- stream generator (RTjpeg_compress, lib/RTjpeg.c:3488-3524, intra only) ----
  * Synthetic frames (gradient + hashed noise, the tests hold a numpy twin):
- * n frames numbered first_frame.., each 1.5*w*h bytes, back to back in d_frames. */
+ * n frames numbered first_frame.., each 1.5*w*h bytes, back to back in d_frames.
+ * The generator and the encoder below make 4:2:0 pictures and streams whatever the instance's format. */
 int mi_rtj_synth_frames(mi_rtj_ctx *ctx, int w, int h, int first_frame, int n, uint32_t seed,
                         int amp, void *d_frames);
 /* The same pictures with the noise generator of SURVEY.md section 8d / BASELINE.md section 2: one linear congruential
@@ -247,6 +278,13 @@ int mi_rtj_encode_stream(mi_rtj_ctx *ctx, int w, int h, int Q, int key_rate, int
 enum { MI_RTJ_RGB32 = 0, MI_RTJ_BGR32 = 1, MI_RTJ_RGB24 = 2, MI_RTJ_BGR24 = 3, MI_RTJ_RGB16 = 4 };
 int mi_rtj_yuv420_to_rgb(mi_rtj_ctx *ctx, int fmt, int w, int h, int n, const void *d_planes,
                          size_t in_frame_stride, void *d_rgb, size_t row_pitch, size_t out_frame_stride);
+
+/* RTjpeg_yuv422rgb24 (lib/RTjpeg.c:3077-3121): n frames of contiguous 4:2:2 planes (Y w x h, Cb and Cr w/2 x h,
+ * in_frame_stride bytes apart) to R, G, B bytes; one Cb/Cr pair per two pixels of every row.  w a multiple of 16, h of 8;
+ * buffers, row pitch and frame strides 16-byte aligned; the bytes of a row past its 3 w are left as they were.
+ * Asynchronous on the instance's stream. */
+int mi_rtj_yuv422_to_rgb24(mi_rtj_ctx *ctx, int w, int h, int n, const void *d_planes, size_t in_frame_stride,
+                           void *d_rgb, size_t row_pitch, size_t out_frame_stride);
 
 /* Measurement aid (SURVEY.md §8d "achievable-copy ceiling"): copies `bytes` (a multiple of 16) from d_src to
  * d_dst `reps` times with a plain 16-byte-per-lane grid-stride kernel and returns the sustained

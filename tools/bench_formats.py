@@ -1,0 +1,137 @@
+"""Throughput of 4:2:2 and greyscale plans (mi_rtj_set_format) on one MI355X, next to the 4:2:0 plan on the same pictures.
+
+    python tools/bench_formats.py [--frames 1024] [--steps 20] [--warmup 3] [--out profiles/formats/bench_formats.json]
+
+Per format: --frames resident packets of 1920x1088 at quality 255 — 16 distinct pictures of the bench content (the
+gradient + LCG noise of bench.py, amplitude 8, seed 12345: tests/rtjlib.py synth_frame_lcg), each packet its own copy in
+the stream buffer — decoded by one plan, one output slot per packet.  4:2:2 pictures take the 4:2:0 chroma lines twice;
+greyscale pictures are the luma plane.  The packets come from the reference's own encoder (oracle/_ref/librtjpeg_ref.so,
+RTjpeg_set_format + RTjpeg_compress); without that library the tool says so and exits with status 2.
+Printed per format: pictures per second from wall time over --steps launches after --warmup, the index's and the
+transform's device time per launch (mi_rtj_plan_times: MI_RTJ_K_EMIT, MI_RTJ_K_DECODE; for 4:2:0 every kernel of its
+path), the algorithmic bytes (packets read once, planes written once) and the transform's share of 8 TB/s with them.
+There is no pass mark: these formats have no earlier figure.  Prints one JSON line."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+HBM_PEAK = 8e12  # bytes per second, nominal
+NAMES = {0: "yuv420", 1: "yuv422", 2: "grey"}
+
+
+def pictures(fmt, w, h, count, F, R):
+    """`count` distinct pictures of the bench content in the format's plane layout"""
+    out = []
+    for i in range(count):
+        p = R.synth_frame_lcg(w, h, i, seed=12345, amp=8)
+        y, u, v = R.split_planes(p, w, h)
+        if fmt == F.FMT_GREY:
+            out.append(y.copy())
+        elif fmt == F.FMT_422:
+            twice = lambda c: np.repeat(c.reshape(h // 2, w // 2), 2, axis=0).reshape(-1)
+            out.append(np.concatenate([y, twice(u), twice(v)]))
+        else:
+            out.append(p)
+    return out
+
+
+def measure(P, F, R, fmt, w, h, n, distinct, steps, warmup):
+    enc = F.RefFmt(fmt)
+    enc.setup_encoder(w, h, 255)
+    distinct_pkts = [enc.encode(p) for p in pictures(fmt, w, h, distinct, F, R)]
+    pkts = [distinct_pkts[i % distinct] for i in range(n)]
+    dev = P.MiRtj()
+    dev.set_format(fmt)
+    d_st, po, pl, hdrs = dev.upload_packets(pkts, align=64)
+    fsz = F.plane_bytes(fmt, w, h)
+    oo = np.arange(n, dtype=np.uint64) * fsz
+    d_out = dev.alloc(fsz * n)
+    dev.memset(d_out, 0, fsz * n)
+    plan = dev.plan(hdrs, po, pl, oo)
+    for _ in range(warmup):
+        plan.decode(d_st, d_out)
+    dev.sync()
+    # the first and the last picture against the checker, so that the figure is of pictures that are right
+    for i in (0, n - 1):
+        got = dev.d2h(d_out, fsz, offset=int(oo[i]))
+        want = np.zeros(fsz, np.uint8)
+        if fmt == F.FMT_420:
+            R.OracleDecoder().decode(pkts[i], want)
+        else:
+            F.Restated(fmt).decode(pkts[i], want)
+        if not np.array_equal(got, want):
+            raise SystemExit(f"{NAMES[fmt]}: picture {i} differs from the checker")
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        plan.decode(d_st, d_out)
+    dev.sync()
+    dt = (time.perf_counter() - t0) / steps
+    plan.profile(True)
+    for _ in range(steps):
+        plan.decode(d_st, d_out)
+    dev.sync()
+    kt, launches = plan.times()
+    device_ms = float(np.median(plan.step_times()))
+    plan.profile(False)
+    info = plan.info()
+    algo = info["bytes_in"] + info["bytes_out"]
+    index_ms = sum(v for k, v in kt.items() if k != "k_decode") / launches
+    decode_ms = kt["k_decode"] / launches
+    res = {"frames": n, "distinct_pictures": distinct, "blocks": info["blocks"], "bytes_in": info["bytes_in"],
+           "bytes_out": info["bytes_out"], "algorithmic_bytes": algo,
+           "frames_per_s": round(n / dt, 1), "ms_per_launch_wall": round(dt * 1e3, 4),
+           "device_ms_per_launch": round(device_ms, 4), "index_ms": round(index_ms, 4), "transform_ms": round(decode_ms, 4),
+           "kernel_ms": {k: round(v / launches, 4) for k, v in kt.items() if v},
+           "transform_share_of_8TBs": round(algo / (decode_ms * 1e-3) / HBM_PEAK, 4),
+           "launch_share_of_8TBs": round(algo / (device_ms * 1e-3) / HBM_PEAK, 4)}
+    plan.close()
+    dev.free(d_st)
+    dev.free(d_out)
+    dev.close()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=1024)
+    ap.add_argument("--distinct", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1088)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    import rtjfmt as F
+    import rtjlib as R
+    if not R.have_reference():
+        print("tools/bench_formats.py: oracle/_ref/librtjpeg_ref.so is missing — the packets of this measurement come from "
+              "the reference's encoder; build the oracle where the reference tree is present", file=sys.stderr)
+        return 2
+    if a.steps < 20:
+        print("tools/bench_formats.py: --steps below 20: not a measurement", file=sys.stderr)
+    P = importlib.import_module("gmerlin-avdecoder_amd")
+    res = {"tool": "bench_formats", "w": a.width, "h": a.height, "quality": 255, "steps": a.steps, "warmup": a.warmup,
+           "content": "bench content: gradient + LCG noise, amplitude 8, seed 12345; packets by the reference encoder"}
+    for fmt in (F.FMT_422, F.FMT_GREY, F.FMT_420):
+        res[NAMES[fmt]] = measure(P, F, R, fmt, a.width, a.height, a.frames, a.distinct, a.steps, a.warmup)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
