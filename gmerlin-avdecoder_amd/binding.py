@@ -33,7 +33,8 @@ EXPORTS = ["mi_rtj_device_count", "mi_rtj_create", "mi_rtj_destroy", "mi_rtj_las
            "mi_rtj_plan_step_times", "mi_rtj_pipe_create", "mi_rtj_pipe_destroy", "mi_rtj_pipe_room",
            "mi_rtj_pipe_pending", "mi_rtj_pipe_submit", "mi_rtj_pipe_next", "mi_rtj_pipe_peek_tag", "mi_rtj_pipe_flush",
            "mi_rtj_pipe_profile", "mi_rtj_pipe_times", "mi_rtj_plan_set_runs", "mi_rtj_plan_run_times",
-           "mi_rtj_plan_run_stats", "mi_rtj_set_format", "mi_rtj_get_format", "mi_rtj_yuv422_to_rgb24"]
+           "mi_rtj_plan_run_stats", "mi_rtj_set_format", "mi_rtj_get_format", "mi_rtj_yuv422_to_rgb24",
+           "mi_rtj_encode_bound_fmt", "mi_rtj_encode_frames_fmt", "mi_rtj_encode_stream_fmt"]
 
 # picture formats (mi_rtj_set_format): RTJ_YUV420 / RTJ_YUV422 / RTJ_RGB8 of the reference
 FMT_YUV420, FMT_YUV422, FMT_GREY = 0, 1, 2
@@ -118,6 +119,11 @@ def load():
                                        C.c_size_t]
     L.mi_rtj_encode_stream.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp,
                                        C.c_int, u64p, u32p]
+    L.mi_rtj_encode_bound_fmt.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.mi_rtj_encode_bound_fmt.restype = C.c_size_t
+    L.mi_rtj_encode_frames_fmt.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, u64p, u32p]
+    L.mi_rtj_encode_stream_fmt.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                           vp, C.c_int, u64p, u32p]
     L.mi_rtj_get_tables.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mi_rtj_copy_ceiling.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
     _LIB = L
@@ -462,12 +468,17 @@ class MiRtj:
         self._chk(self.L.mi_rtj_synth_frames_lcg(self.h, w, h, first, n, seed, amp, d))
         return d
 
-    def encode_bound(self, w, h, n, align=64):
-        return self.L.mi_rtj_encode_bound(w, h, n, align)
+    def encode_bound(self, w, h, n, align=64, fmt=FMT_YUV420):
+        if fmt == FMT_YUV420:
+            return self.L.mi_rtj_encode_bound(w, h, n, align)
+        return self.L.mi_rtj_encode_bound_fmt(int(fmt), w, h, n, align)
 
-    def encode(self, w, h, Q, n, d_frames, align=64, key_rate=0, lmask=0, cmask=0, d_stream=None):
+    def encode(self, w, h, Q, n, d_frames, align=64, key_rate=0, lmask=0, cmask=0, d_stream=None, fmt=FMT_YUV420):
         """Intra batch (key_rate 0) or one in-order stream with skip blocks (key_rate > 0).  d_stream: a buffer of
-        encode_bound() bytes the caller allocated (else one is allocated here)."""
+        encode_bound() bytes the caller allocated (else one is allocated here).  fmt: the pictures' format (FMT_YUV422:
+        Y, Cb, Cr of 2 w h bytes; FMT_GREY: Y alone); it is the call's, not the instance's (set_format)."""
+        if fmt != FMT_YUV420:
+            return self._encode_fmt(int(fmt), w, h, Q, n, d_frames, align, key_rate, lmask, cmask, d_stream)
         bound = self.L.mi_rtj_encode_bound(w, h, n, align)
         if d_stream is None:
             d_stream = self.alloc(bound)
@@ -480,3 +491,21 @@ class MiRtj:
             self._chk(self.L.mi_rtj_encode_frames(self.h, w, h, Q, n, d_frames, d_stream, align,
                                                   po.ctypes.data_as(u64p), pl.ctypes.data_as(u32p)))
         return d_stream, po, pl
+
+    def _encode_fmt(self, fmt, w, h, Q, n, d_frames, align, key_rate, lmask, cmask, d_stream):
+        """encode() for 4:2:2 and greyscale pictures: mi_rtj_encode_frames_fmt / mi_rtj_encode_stream_fmt"""
+        own = d_stream is None
+        if own:
+            d_stream = self.alloc(max(self.L.mi_rtj_encode_bound_fmt(fmt, w, h, n, align), 1))
+        po = np.zeros(max(n, 1), np.uint64)
+        pl = np.zeros(max(n, 1), np.uint32)
+        pop, plp = po.ctypes.data_as(u64p), pl.ctypes.data_as(u32p)
+        if key_rate > 0:
+            rc = self.L.mi_rtj_encode_stream_fmt(self.h, fmt, w, h, Q, key_rate, lmask, cmask, n, d_frames, d_stream,
+                                                 align, pop, plp)
+        else:
+            rc = self.L.mi_rtj_encode_frames_fmt(self.h, fmt, w, h, Q, n, d_frames, d_stream, align, pop, plp)
+        if rc != 0 and own:  # a refused call (the library names the rule) leaves nothing allocated
+            self.free(d_stream)
+        self._chk(rc)
+        return d_stream, po[:n], pl[:n]

@@ -21,6 +21,7 @@
 #include "rtj_common.h"
 #include "rtj_decode_chroma.h"
 #include "rtj_decode_kernels.h"
+#include "rtj_encode_fmt_kernels.h"
 #include "rtj_encode_kernels.h"
 #include "rtj_format_kernels.h"
 #include "rtj_index_kernels.h"
@@ -2232,15 +2233,49 @@ size_t mi_rtj_encode_bound(int w, int h, int n, int align) {
   return (size_t)n * ((per + align - 1) / align * align) + align;
 }
 
+size_t mi_rtj_encode_bound_fmt(int fmt, int w, int h, int n, int align) {
+  if (fmt == MI_RTJ_FMT_YUV420) return mi_rtj_encode_bound(w, h, n, align);
+  if ((fmt != MI_RTJ_FMT_YUV422 && fmt != MI_RTJ_FMT_GREY) || w <= 0 || h <= 0 || n <= 0 || align < 1) return 0;
+  const size_t nblk = fmt == MI_RTJ_FMT_YUV422 ? (size_t)(w / 16) * (h / 8) * 4 : (size_t)(w / 8) * (h / 8);
+  const size_t per = MI_RTJ_HEADER_SIZE + nblk * 64;
+  return (size_t)n * ((per + align - 1) / align * align) + align;
+}
+
 }  // extern "C" (reopened below)
 
 namespace {
-// shared body of the intra batch encoder and the in-order inter (skip-block) stream encoder
-int encode_impl(mi_rtj_ctx* c, int w, int h, int Q, int key_rate, int lmask, int cmask, int n, const void* d_frames,
+// the format's kernel of one pass: m pictures (kInter: one) from `frames` into block slots and lengths
+template <bool kInter>
+void launch_encode_fmt(int fmt, hipStream_t st, const uint8_t* frames, int w, int h, int m, const QTab* qt, uint8_t* slots,
+                       uint8_t* lens, int16_t* old, int lmask, int cmask) {
+  const unsigned units = fmt == MI_RTJ_FMT_YUV422 ? (unsigned)(w / 16) * (unsigned)(h / 8) : (unsigned)(w / 8) * (unsigned)(h / 8);
+  const unsigned groups = (units + fmt_units_per_group(fmt) - 1u) / fmt_units_per_group(fmt);
+  const dim3 grid(fmt_parts(fmt) * groups, (unsigned)m);
+  if (fmt == MI_RTJ_FMT_YUV422)
+    hipLaunchKernelGGL((k_encode_fmt<kFmtYUV422, kInter>), grid, dim3(64), 0, st, frames, w, h, qt, slots, lens, old, lmask, cmask);
+  else
+    hipLaunchKernelGGL((k_encode_fmt<kFmtGrey, kInter>), grid, dim3(64), 0, st, frames, w, h, qt, slots, lens, old, lmask, cmask);
+}
+
+// shared body of the intra batch encoder and the in-order inter (skip-block) stream encoder, all formats
+int encode_impl(mi_rtj_ctx* c, int fmt, int w, int h, int Q, int key_rate, int lmask, int cmask, int n, const void* d_frames,
                 void* d_stream, int align, uint64_t* pkt_offset, uint32_t* pkt_len) {
-  if (!c || !d_frames || !d_stream || !pkt_offset || !pkt_len || w <= 0 || h <= 0 || (w & 15) || (h & 15) ||
-      n <= 0 || align < 1 || (align & (align - 1)))
-    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: bad argument");
+  if (fmt == MI_RTJ_FMT_YUV420) {
+    if (!c || !d_frames || !d_stream || !pkt_offset || !pkt_len || w <= 0 || h <= 0 || (w & 15) || (h & 15) ||
+        n <= 0 || align < 1 || (align & (align - 1)))
+      return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: bad argument");
+  } else {
+    if (fmt != MI_RTJ_FMT_YUV422 && fmt != MI_RTJ_FMT_GREY)
+      return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: unknown format %d (0 = 4:2:0, 1 = 4:2:2, 2 = greyscale)", fmt);
+    if (!c || !d_frames || !d_stream || !pkt_offset || !pkt_len || n <= 0 || align < 1 || (align & (align - 1)))
+      return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: bad argument (NULL buffer, no pictures, or align not a power of two)");
+    if (fmt == MI_RTJ_FMT_YUV422 && (w <= 0 || h <= 0 || (w & 15) || (h & 7)))
+      return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: %dx%d: a 4:2:2 picture's width is a positive multiple of 16, its height "
+                  "a positive multiple of 8", w, h);
+    if (fmt == MI_RTJ_FMT_GREY && (w <= 0 || h <= 0 || (w & 7) || (h & 7)))
+      return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: %dx%d: a greyscale picture's width and height are positive multiples of 8",
+                  w, h);
+  }
   if (Q < 1) Q = 1;
   if (Q > 255) Q = 255;
   // RTjpeg_set_intra's clamps (lib/RTjpeg.c:2459-2468)
@@ -2249,8 +2284,9 @@ int encode_impl(mi_rtj_ctx* c, int w, int h, int Q, int key_rate, int lmask, int
   cmask = cmask < 0 ? 0 : (cmask > 16 ? 16 : cmask);
   const bool inter = key_rate > 0;
   HIPCHK(c, hipSetDevice(c->device));
-  const uint32_t nblk = (uint32_t)(w / 16) * (h / 16) * 6;
-  const size_t fsz = (size_t)w * h * 3 / 2;
+  const uint32_t nblk = fmt == MI_RTJ_FMT_YUV422 ? (uint32_t)(w / 16) * (h / 8) * 4
+                        : fmt == MI_RTJ_FMT_GREY ? (uint32_t)(w / 8) * (h / 8) : (uint32_t)(w / 16) * (h / 16) * 6;
+  const size_t fsz = fmt == MI_RTJ_FMT_YUV422 ? (size_t)w * h * 2 : fmt == MI_RTJ_FMT_GREY ? (size_t)w * h : (size_t)w * h * 3 / 2;
   // frames per pass: inter frames depend on each other, intra ones do not (256: 0.8 GB of block slots at 1080p)
   const int chunk = inter ? 1 : (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)1 << 30) / ((size_t)nblk * 64)));
   uint8_t *slots = nullptr, *lens = nullptr;
@@ -2296,7 +2332,11 @@ int encode_impl(mi_rtj_ctx* c, int w, int h, int Q, int key_rate, int lmask, int
     const size_t tot = (size_t)m * nblk;
     // RTjpeg_compress: the previous-block store is cleared whenever key_count is 0 (lib/RTjpeg.c:3504-3505)
     if (inter && key_count == 0) ENC_CHK(hipMemsetAsync(old, 0, (size_t)nblk * 64 * sizeof(int16_t), c->stream));
-    if (inter) {
+    if (fmt != MI_RTJ_FMT_YUV420) {  // one wave per 64 blocks, inter pictures too (rtj_encode_fmt_kernels.h)
+      const uint8_t* fr = (const uint8_t*)d_frames + (size_t)f0 * fsz;
+      if (inter) launch_encode_fmt<true>(fmt, c->stream, fr, w, h, m, c->d_lut + Q, slots, lens, old, lmask, cmask);
+      else launch_encode_fmt<false>(fmt, c->stream, fr, w, h, m, c->d_lut + Q, slots, lens, nullptr, 0, 0);
+    } else if (inter) {
       hipLaunchKernelGGL(k_encode_blocks, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
                          (const uint8_t*)d_frames + (size_t)f0 * fsz, w, h, m, c->d_lut + Q, slots, lens, old, lmask, cmask);
     } else {  // intra: a wave per 64 horizontally adjacent blocks (rtj_encode_kernels.h)
@@ -2326,12 +2366,22 @@ extern "C" {
 
 int mi_rtj_encode_frames(mi_rtj_ctx* c, int w, int h, int Q, int n, const void* d_frames, void* d_stream, int align,
                          uint64_t* pkt_offset, uint32_t* pkt_len) {
-  return encode_impl(c, w, h, Q, 0, 0, 0, n, d_frames, d_stream, align, pkt_offset, pkt_len);
+  return encode_impl(c, MI_RTJ_FMT_YUV420, w, h, Q, 0, 0, 0, n, d_frames, d_stream, align, pkt_offset, pkt_len);
+}
+
+int mi_rtj_encode_frames_fmt(mi_rtj_ctx* c, int fmt, int w, int h, int Q, int n, const void* d_frames, void* d_stream,
+                             int align, uint64_t* pkt_offset, uint32_t* pkt_len) {
+  return encode_impl(c, fmt, w, h, Q, 0, 0, 0, n, d_frames, d_stream, align, pkt_offset, pkt_len);
 }
 
 int mi_rtj_encode_stream(mi_rtj_ctx* c, int w, int h, int Q, int key_rate, int lmask, int cmask, int n,
                          const void* d_frames, void* d_stream, int align, uint64_t* pkt_offset, uint32_t* pkt_len) {
-  return encode_impl(c, w, h, Q, key_rate, lmask, cmask, n, d_frames, d_stream, align, pkt_offset, pkt_len);
+  return encode_impl(c, MI_RTJ_FMT_YUV420, w, h, Q, key_rate, lmask, cmask, n, d_frames, d_stream, align, pkt_offset, pkt_len);
+}
+
+int mi_rtj_encode_stream_fmt(mi_rtj_ctx* c, int fmt, int w, int h, int Q, int key_rate, int lmask, int cmask, int n,
+                             const void* d_frames, void* d_stream, int align, uint64_t* pkt_offset, uint32_t* pkt_len) {
+  return encode_impl(c, fmt, w, h, Q, key_rate, lmask, cmask, n, d_frames, d_stream, align, pkt_offset, pkt_len);
 }
 
 int mi_rtj_yuv420_to_rgb(mi_rtj_ctx* c, int fmt, int w, int h, int n, const void* d_planes, size_t in_frame_stride,

@@ -246,7 +246,8 @@ int mi_rtj_plan_read_index(mi_rtj_plan *plan, uint32_t *dst, size_t max_entries)
 /* ---- stream generator (RTjpeg_compress, lib/RTjpeg.c:3488-3524, intra only) ----
  * Synthetic frames (gradient + hashed noise, the tests hold a numpy twin):
  * n frames numbered first_frame.., each 1.5*w*h bytes, back to back in d_frames.
- * The generator and the encoder below make 4:2:0 pictures and streams whatever the instance's format. */
+ * The generator makes 4:2:0 pictures whatever the instance's format.  The encoder entry points below take 4:2:0
+ * pictures; their _fmt forms take the format as an argument.  None of them reads or fixes the instance's format. */
 int mi_rtj_synth_frames(mi_rtj_ctx *ctx, int w, int h, int first_frame, int n, uint32_t seed,
                         int amp, void *d_frames);
 /* The same pictures with the noise generator of SURVEY.md section 8d / BASELINE.md section 2: one linear congruential
@@ -269,6 +270,36 @@ int mi_rtj_encode_frames(mi_rtj_ctx *ctx, int w, int h, int Q, int n, const void
 int mi_rtj_encode_stream(mi_rtj_ctx *ctx, int w, int h, int Q, int key_rate, int lmask, int cmask, int n,
                          const void *d_frames, void *d_stream, int align, uint64_t *pkt_offset,
                          uint32_t *pkt_len);
+
+/* ---- the encoder in the other two formats: the arms of RTjpeg_compress's switch (lib/RTjpeg.c:3488-3524) ----
+ * The three calls above with the picture format as an argument (MI_RTJ_FMT_*).  The format belongs to the call: the
+ * instance's mi_rtj_set_format state is neither read nor fixed by encoding, so one instance can encode in a format and
+ * decode in another.  With MI_RTJ_FMT_YUV420 they are the calls above, byte for byte.
+ *   MI_RTJ_FMT_YUV422  RTjpeg_compressYUV422 / RTjpeg_mcompressYUV422 (lib/RTjpeg.c:2565-2608, 2924-2988).  Width a
+ *                      positive multiple of 16, height a positive multiple of 8.  A picture is Y w x h, then Cb and Cr
+ *                      w/2 x h, contiguous, 2 w h bytes; blocks per 16x8 macroblock: Y, Y (luma tables), Cb, Cr (chroma
+ *                      tables, stride w/2); 4 w h / 128 blocks.
+ *   MI_RTJ_FMT_GREY    RTjpeg_compress8 / RTjpeg_mcompress8 (lib/RTjpeg.c:2610-2637, 2990-3018).  Width and height
+ *                      positive multiples of 8.  One plane, w h bytes; blocks in raster order, luma tables; w h / 64
+ *                      blocks.  Block (row r, column c) codes lines 8r .. 8r+7, pixels 8c .. 8c+7 at line stride w: the
+ *                      picture it is given, which is the picture RTjpeg_decompress8 puts back.  This departs on purpose
+ *                      from the reference's reads: its greyscale arms pass RTjpeg_dctY the width where every other arm
+ *                      passes width / 8 (:2626, :3004; RTjpeg_dctY advances by rskip << 3, :341), so a block is read at a
+ *                      line stride of 8 w, and the intra arm advances one line per block row (:2630): block row r reads
+ *                      lines r, r+8, .., r+56 and, for small heights, past the plane.  Transform, quantiser, coding,
+ *                      unchanged-block test and header are the reference's (DESIGN.md section 11.1 says how that is held).
+ * n pictures back to back in d_frames.  Any other size, an unknown format, a NULL buffer, n <= 0 or an align that is no
+ * power of two returns MI_RTJ_ERR_ARG with a message that names the rule, before anything is allocated.
+ * Header (:3516-3522), Q clamped to 1..255, RTjpeg_set_intra's clamps, the previous-block store cleared whenever the key
+ * count is 0 and the key byte counting 0..key_rate are those of mi_rtj_encode_frames / mi_rtj_encode_stream.
+ * mi_rtj_encode_bound_fmt: 12 + 64 bytes per block of the format, each packet aligned, as mi_rtj_encode_bound; 0 for a
+ * bad argument.  Synchronous, like the calls above. */
+size_t mi_rtj_encode_bound_fmt(int fmt, int w, int h, int n, int align);
+int mi_rtj_encode_frames_fmt(mi_rtj_ctx *ctx, int fmt, int w, int h, int Q, int n, const void *d_frames,
+                             void *d_stream, int align, uint64_t *pkt_offset, uint32_t *pkt_len);
+int mi_rtj_encode_stream_fmt(mi_rtj_ctx *ctx, int fmt, int w, int h, int Q, int key_rate, int lmask, int cmask, int n,
+                             const void *d_frames, void *d_stream, int align, uint64_t *pkt_offset,
+                             uint32_t *pkt_len);
 
 /* ---- colour stage: RTjpeg_yuv420rgb32 / bgr32 / rgb24 / bgr24 / rgb16
  * (lib/RTjpeg.c:3123-3475), device resident.  n frames of contiguous Y,U,V planes (in_frame_stride
