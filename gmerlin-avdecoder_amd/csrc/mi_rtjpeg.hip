@@ -21,7 +21,6 @@
 #include "rtj_common.h"
 #include "rtj_decode_chroma.h"
 #include "rtj_decode_kernels.h"
-#include "rtj_encode_fmt_kernels.h"
 #include "rtj_encode_kernels.h"
 #include "rtj_format_kernels.h"
 #include "rtj_index_kernels.h"
@@ -44,6 +43,44 @@ struct Timed {
   hipEvent_t a = nullptr, b = nullptr;
   bool owns_a = true;  // false: `a` is the previous kernel's `b` (kernels run back to back on one stream)
 };
+
+// The three picture formats, one row each, indexed by MI_RTJ_FMT_*: the numbers are FmtShape's (rtj_common.h), the
+// texts are what the entry points say about the format.  Every size the host derives from a format comes from here.
+struct Format {
+  uint32_t mb_w, mb_h;  // macroblock, pixels (lib/RTjpeg.c:2651-2653 and 2761-2763 are these loops' steps)
+  uint32_t blk_per_mb, parts, units_per_group;
+  uint32_t chroma_planes, chroma_sx, chroma_sy;  // chroma planes are (w >> sx) x (h >> sy)
+  const char* name;
+  const char* abi_name;
+  const char* header_rule;  // after "packet header WxH: "
+  const char* encode_rule;  // after "mi_rtj_encode: WxH: " (4:2:0 has one message for every bad argument)
+
+  bool geometry_ok(int w, int h) const { return w > 0 && h > 0 && w % (int)mb_w == 0 && h % (int)mb_h == 0; }
+  uint32_t units_per_row(int w) const { return (uint32_t)w / mb_w; }
+  uint64_t units(int w, int h) const { return (uint64_t)units_per_row(w) * ((uint32_t)h / mb_h); }  // macroblocks
+  uint64_t blocks(int w, int h) const { return units(w, h) * blk_per_mb; }
+  uint32_t groups(uint32_t units) const { return (units + units_per_group - 1u) / units_per_group; }
+  size_t chroma_plane_bytes(size_t w, size_t h) const { return chroma_planes ? (w >> chroma_sx) * (h >> chroma_sy) : 0; }
+  size_t picture_bytes(size_t w, size_t h) const { return w * h + chroma_planes * chroma_plane_bytes(w, h); }
+};
+template <int Fmt>
+constexpr Format format_row(const char* name, const char* abi_name, const char* header_rule, const char* encode_rule) {
+  using S = FmtShape<Fmt>;
+  return {S::kMbW, S::kMbH, S::kBlkPerMb, S::kParts, S::kUnitsPerGroup, S::kChromaPlanes, S::kChromaShiftX,
+          S::kChromaShiftY, name, abi_name, header_rule, encode_rule};
+}
+constexpr Format kFormats[] = {
+    format_row<kFmtYUV420>("4:2:0", "4:2:0 (MI_RTJ_FMT_YUV420)", "width and height must be positive multiples of 16", ""),
+    format_row<kFmtYUV422>("4:2:2", "4:2:2 (MI_RTJ_FMT_YUV422)",
+                           "a 4:2:2 picture needs a positive width that is a multiple of 16 and a positive height that is a multiple of 8",
+                           "a 4:2:2 picture's width is a positive multiple of 16, its height a positive multiple of 8"),
+    format_row<kFmtGrey>("greyscale", "greyscale (MI_RTJ_FMT_GREY)",
+                         "a greyscale picture needs a positive width and height that are multiples of 8",
+                         "a greyscale picture's width and height are positive multiples of 8"),
+};
+static_assert(MI_RTJ_FMT_YUV420 == kFmtYUV420 && MI_RTJ_FMT_YUV422 == kFmtYUV422 && MI_RTJ_FMT_GREY == kFmtGrey,
+              "kFormats is indexed by the ABI's format numbers");
+inline bool format_known(int fmt) { return fmt >= 0 && fmt < (int)(sizeof kFormats / sizeof kFormats[0]); }
 
 }  // namespace
 
@@ -298,14 +335,8 @@ bool device_is_gfx950(int dev) {
 // Returns the LUT row to use, or a negative error.
 int apply_header(mi_rtj_ctx* c, const uint8_t* hdr, int* w, int* h) {
   const int hw = hdr[6] | (hdr[7] << 8), hh = hdr[8] | (hdr[9] << 8), q = hdr[10];
-  if (c->fmt == MI_RTJ_FMT_YUV422) {  // the loops of lib/RTjpeg.c:2651-2653 step 8 lines and 16 columns
-    if (hw <= 0 || hh <= 0 || (hw & 15) || (hh & 7))
-      return fail(c, MI_RTJ_ERR_GEOMETRY, "packet header %dx%d: a 4:2:2 picture needs a positive width that is a multiple of 16 and a positive height that is a multiple of 8", hw, hh);
-  } else if (c->fmt == MI_RTJ_FMT_GREY) {  // lib/RTjpeg.c:2761-2763 step 8 lines and 8 columns
-    if (hw <= 0 || hh <= 0 || (hw & 7) || (hh & 7))
-      return fail(c, MI_RTJ_ERR_GEOMETRY, "packet header %dx%d: a greyscale picture needs a positive width and height that are multiples of 8", hw, hh);
-  } else if (hw <= 0 || hh <= 0 || (hw & 15) || (hh & 15))
-    return fail(c, MI_RTJ_ERR_GEOMETRY, "packet header %dx%d: width and height must be positive multiples of 16", hw, hh);
+  const Format& F = kFormats[c->fmt];
+  if (!F.geometry_ok(hw, hh)) return fail(c, MI_RTJ_ERR_GEOMETRY, "packet header %dx%d: %s", hw, hh, F.header_rule);
   c->width = hw;
   c->height = hh;
   if (q != c->Q) c->Q = q < 1 ? 1 : q;  // RTjpeg_set_quality clamps to 1..255 (lib/RTjpeg.c:2410-2411)
@@ -329,17 +360,10 @@ int fill_frame(mi_rtj_ctx* c, const uint8_t* hdr, uint64_t pkt_off, uint32_t pkt
   f->h = (uint32_t)h;
   f->qidx = (uint32_t)q;
   f->blk_base = blk_base;
-  if (c->fmt == MI_RTJ_FMT_YUV422) {  // macroblock = 16x8 pixels: Y Y Cb Cr
-    f->mbw = (uint32_t)w / 16;
-    f->nmb = f->mbw * ((uint32_t)h / 8);
-  } else if (c->fmt == MI_RTJ_FMT_GREY) {  // "macroblock" = one 8x8 block
-    f->mbw = (uint32_t)w / 8;
-    f->nmb = f->mbw * ((uint32_t)h / 8);
-  } else {
-    f->mbw = (uint32_t)w / 16;
-    f->nmb = f->mbw * ((uint32_t)h / 16);
-  }
-  if ((uint64_t)f->nmb * fmt_blocks_per_mb(c->fmt) * 64 + kAllocPad >= 0xFFFFFFFFull)  // block offsets and the walkers' positions are 32-bit
+  const Format& F = kFormats[c->fmt];
+  f->mbw = F.units_per_row(w);
+  f->nmb = (uint32_t)F.units(w, h);  // (a header's 16-bit sizes: at most 2^26 units)
+  if (F.blocks(w, h) * 64 + kAllocPad >= 0xFFFFFFFFull)  // block offsets and the walkers' positions are 32-bit
     return fail(c, MI_RTJ_ERR_GEOMETRY, "picture of %dx%d: its worst-case stream does not fit 32-bit offsets", w, h);
   f->nchunks = (f->data_len + kChunk - 1) / kChunk;
   if (f->nchunks == 0) f->nchunks = 1;
@@ -347,14 +371,9 @@ int fill_frame(mi_rtj_ctx* c, const uint8_t* hdr, uint64_t pkt_off, uint32_t pkt
 }
 
 // blocks, macroblock groups and plane bytes of a picture in the plan's format
-inline uint64_t frame_blocks(const FrameDev& f, int fmt) { return (uint64_t)f.nmb * fmt_blocks_per_mb(fmt); }
-inline uint32_t frame_groups(const FrameDev& f, int fmt) {
-  return (f.nmb + fmt_units_per_group(fmt) - 1u) / fmt_units_per_group(fmt);
-}
-inline size_t frame_plane_bytes(const FrameDev& f, int fmt) {
-  const size_t ysz = (size_t)f.w * f.h;
-  return fmt == MI_RTJ_FMT_YUV422 ? 2 * ysz : fmt == MI_RTJ_FMT_GREY ? ysz : ysz * 3 / 2;
-}
+inline uint64_t frame_blocks(const FrameDev& f, int fmt) { return (uint64_t)f.nmb * kFormats[fmt].blk_per_mb; }
+inline uint32_t frame_groups(const FrameDev& f, int fmt) { return kFormats[fmt].groups(f.nmb); }
+inline size_t frame_plane_bytes(const FrameDev& f, int fmt) { return kFormats[fmt].picture_bytes(f.w, f.h); }
 
 // per-chunk scratch of a plan (re)sized for its frames; chunk_base / sum_base are set here
 int plan_alloc_chunks(mi_rtj_plan* p) {
@@ -497,7 +516,7 @@ int plan_launch_fmt(mi_rtj_plan* p, const uint8_t* st, uint8_t* out) {
     HIPCHK(c, hipEventRecord(ti.a, ds));
   }
   const dim3 igrid(std::min<unsigned>((unsigned)p->n, 16384u)), block(kDecThreads);
-  const dim3 dgrid(fmt_parts(p->fmt) * p->max_groups, (unsigned)p->n);
+  const dim3 dgrid(kFormats[p->fmt].parts * p->max_groups, (unsigned)p->n);
   if (p->fmt == MI_RTJ_FMT_YUV422)
     hipLaunchKernelGGL(k_index_fmt<kFmtYUV422>, igrid, dim3(64), 0, ds, p->d_frames, (uint32_t)p->n, st, c->d_lut, p->d_blkoff);
   else
@@ -899,7 +918,7 @@ const char* mi_rtj_last_error(const mi_rtj_ctx* c) {
 
 int mi_rtj_set_format(mi_rtj_ctx* c, int fmt) {
   if (!c) return MI_RTJ_ERR_ARG;
-  if (fmt != MI_RTJ_FMT_YUV420 && fmt != MI_RTJ_FMT_YUV422 && fmt != MI_RTJ_FMT_GREY)
+  if (!format_known(fmt))
     return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_set_format: unknown format %d (0 = 4:2:0, 1 = 4:2:2, 2 = greyscale)", fmt);
   if (c->fmt_fixed && fmt != c->fmt)
     return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_set_format: the instance has decoded, planned or opened a session in format %d; "
@@ -1290,7 +1309,7 @@ int mi_rtj_plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len) {
   if (n_runs < 0 || (n_runs > 0 && !run_len)) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: bad argument");
   if (p->fmt != MI_RTJ_FMT_YUV420)
     return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: runs are for 4:2:0 plans; this plan's format is %s",
-                p->fmt == MI_RTJ_FMT_YUV422 ? "4:2:2" : "greyscale");
+                kFormats[p->fmt].name);
   // ---- check everything before anything changes: a refused call leaves the plan as it was ----
   std::vector<RunDev> runs;
   std::vector<RunChunkDev> chunks;
@@ -1491,18 +1510,18 @@ int mi_rtj_decode(mi_rtj_ctx* c, const uint8_t* pkt, size_t len, uint8_t* const 
   if (dst) {
     // gavl_video_frame_copy(format, f, priv->frame) (lib/video_rtjpeg.c:82): image_width x
     // image_height region, each side's own strides — done by the copy engine on the way out.
-    const bool grey = c->fmt == MI_RTJ_FMT_GREY;  // one plane: dst[1], dst[2] and their strides are not looked at
+    const Format& F = kFormats[c->fmt];
+    const bool grey = F.chroma_planes == 0;  // one plane: dst[1], dst[2] and their strides are not looked at
     if (!dst[0] || (!grey && (!dst[1] || !dst[2])) || !dst_stride) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_decode: NULL plane");
     if (crop_w <= 0 || crop_h <= 0 || crop_w > (int)f.w || crop_h > (int)f.h)
       return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_decode: crop %dx%d outside the coded %ux%u picture", crop_w, crop_h, f.w, f.h);
-    const size_t ysz = (size_t)f.w * f.h;
-    // chroma: half the width; half the height too in 4:2:0, every line in 4:2:2
-    const size_t csz = c->fmt == MI_RTJ_FMT_YUV422 ? ysz / 2 : ysz / 4;
-    const int cw = (crop_w + 1) / 2, ch = c->fmt == MI_RTJ_FMT_YUV422 ? crop_h : (crop_h + 1) / 2;
+    const size_t ysz = (size_t)f.w * f.h, csz = F.chroma_plane_bytes(f.w, f.h), cstride = f.w >> F.chroma_sx;
+    // chroma: half the width; half the height too in 4:2:0, every line in 4:2:2 (a cropped odd size rounds up)
+    const int cw = (crop_w + (1 << F.chroma_sx) - 1) >> F.chroma_sx, ch = (crop_h + (1 << F.chroma_sy) - 1) >> F.chroma_sy;
     HIPCHK(c, hipMemcpy2DAsync(dst[0], (size_t)dst_stride[0], c->d_frame, f.w, (size_t)crop_w, (size_t)crop_h, hipMemcpyDeviceToHost, c->stream));
     if (!grey) {
-      HIPCHK(c, hipMemcpy2DAsync(dst[1], (size_t)dst_stride[1], c->d_frame + ysz, f.w / 2, (size_t)cw, (size_t)ch, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpy2DAsync(dst[2], (size_t)dst_stride[2], c->d_frame + ysz + csz, f.w / 2, (size_t)cw, (size_t)ch, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpy2DAsync(dst[1], (size_t)dst_stride[1], c->d_frame + ysz, cstride, (size_t)cw, (size_t)ch, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpy2DAsync(dst[2], (size_t)dst_stride[2], c->d_frame + ysz + csz, cstride, (size_t)cw, (size_t)ch, hipMemcpyDeviceToHost, c->stream));
     }
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1514,6 +1533,7 @@ int mi_rtj_decode_nocopy(mi_rtj_ctx* c, const uint8_t* pkt, size_t len, const ui
   const int r = decode_one_launch(c, pkt, len);
   if (r != MI_RTJ_OK) return r;
   const FrameDev& f = c->single->h_frames[0];
+  const Format& F = kFormats[c->fmt];
   const size_t ysz = (size_t)f.w * f.h, fsz = frame_plane_bytes(f, c->fmt);
   if (fsz > c->h_frame_cap) {
     if (c->h_frame) (void)hipHostFree(c->h_frame);
@@ -1525,14 +1545,14 @@ int mi_rtj_decode_nocopy(mi_rtj_ctx* c, const uint8_t* pkt, size_t len, const ui
   HIPCHK(c, hipStreamSynchronize(c->stream));
   planes[0] = c->h_frame;
   strides[0] = (int)f.w;
-  if (c->fmt == MI_RTJ_FMT_GREY) {
+  if (F.chroma_planes == 0) {
     planes[1] = planes[2] = nullptr;
     strides[1] = strides[2] = 0;
     return MI_RTJ_OK;
   }
   planes[1] = c->h_frame + ysz;
-  planes[2] = c->h_frame + ysz + (c->fmt == MI_RTJ_FMT_YUV422 ? ysz / 2 : ysz / 4);
-  strides[1] = strides[2] = (int)f.w / 2;
+  planes[2] = planes[1] + F.chroma_plane_bytes(f.w, f.h);
+  strides[1] = strides[2] = (int)(f.w >> F.chroma_sx);
   return MI_RTJ_OK;
 }
 
@@ -1748,7 +1768,7 @@ mi_rtj_pipe* mi_rtj_pipe_create(mi_rtj_ctx* c, int depth, int max_w, int max_h) 
   }
   if (c->fmt != MI_RTJ_FMT_YUV420) {
     fail(c, MI_RTJ_ERR_ARG, "mi_rtj_pipe_create: sessions decode 4:2:0 streams only; this instance's format is %s",
-         c->fmt == MI_RTJ_FMT_YUV422 ? "4:2:2 (MI_RTJ_FMT_YUV422)" : "greyscale (MI_RTJ_FMT_GREY)");
+         kFormats[c->fmt].abi_name);
     return nullptr;
   }
   if (hipSetDevice(c->device) != hipSuccess) {
@@ -2227,19 +2247,14 @@ int mi_rtj_synth_frames_lcg(mi_rtj_ctx* c, int w, int h, int first, int n, uint3
   return MI_RTJ_OK;
 }
 
-size_t mi_rtj_encode_bound(int w, int h, int n, int align) {
-  if (w <= 0 || h <= 0 || n <= 0 || align < 1) return 0;
-  const size_t per = MI_RTJ_HEADER_SIZE + (size_t)(w / 16) * (h / 16) * 6 * 64;
+// every block at its longest, 64 bytes; sizes that are no multiple of the macroblock round down, as they always have
+size_t mi_rtj_encode_bound_fmt(int fmt, int w, int h, int n, int align) {
+  if (!format_known(fmt) || w <= 0 || h <= 0 || n <= 0 || align < 1) return 0;
+  const size_t per = MI_RTJ_HEADER_SIZE + (size_t)kFormats[fmt].blocks(w, h) * 64;
   return (size_t)n * ((per + align - 1) / align * align) + align;
 }
 
-size_t mi_rtj_encode_bound_fmt(int fmt, int w, int h, int n, int align) {
-  if (fmt == MI_RTJ_FMT_YUV420) return mi_rtj_encode_bound(w, h, n, align);
-  if ((fmt != MI_RTJ_FMT_YUV422 && fmt != MI_RTJ_FMT_GREY) || w <= 0 || h <= 0 || n <= 0 || align < 1) return 0;
-  const size_t nblk = fmt == MI_RTJ_FMT_YUV422 ? (size_t)(w / 16) * (h / 8) * 4 : (size_t)(w / 8) * (h / 8);
-  const size_t per = MI_RTJ_HEADER_SIZE + nblk * 64;
-  return (size_t)n * ((per + align - 1) / align * align) + align;
-}
+size_t mi_rtj_encode_bound(int w, int h, int n, int align) { return mi_rtj_encode_bound_fmt(MI_RTJ_FMT_YUV420, w, h, n, align); }
 
 }  // extern "C" (reopened below)
 
@@ -2248,10 +2263,11 @@ namespace {
 template <bool kInter>
 void launch_encode_fmt(int fmt, hipStream_t st, const uint8_t* frames, int w, int h, int m, const QTab* qt, uint8_t* slots,
                        uint8_t* lens, int16_t* old, int lmask, int cmask) {
-  const unsigned units = fmt == MI_RTJ_FMT_YUV422 ? (unsigned)(w / 16) * (unsigned)(h / 8) : (unsigned)(w / 8) * (unsigned)(h / 8);
-  const unsigned groups = (units + fmt_units_per_group(fmt) - 1u) / fmt_units_per_group(fmt);
-  const dim3 grid(fmt_parts(fmt) * groups, (unsigned)m);
-  if (fmt == MI_RTJ_FMT_YUV422)
+  const Format& F = kFormats[fmt];
+  const dim3 grid(F.parts * F.groups((uint32_t)F.units(w, h)), (unsigned)m);
+  if (fmt == MI_RTJ_FMT_YUV420)
+    hipLaunchKernelGGL((k_encode_fmt<kFmtYUV420, kInter>), grid, dim3(64), 0, st, frames, w, h, qt, slots, lens, old, lmask, cmask);
+  else if (fmt == MI_RTJ_FMT_YUV422)
     hipLaunchKernelGGL((k_encode_fmt<kFmtYUV422, kInter>), grid, dim3(64), 0, st, frames, w, h, qt, slots, lens, old, lmask, cmask);
   else
     hipLaunchKernelGGL((k_encode_fmt<kFmtGrey, kInter>), grid, dim3(64), 0, st, frames, w, h, qt, slots, lens, old, lmask, cmask);
@@ -2260,21 +2276,16 @@ void launch_encode_fmt(int fmt, hipStream_t st, const uint8_t* frames, int w, in
 // shared body of the intra batch encoder and the in-order inter (skip-block) stream encoder, all formats
 int encode_impl(mi_rtj_ctx* c, int fmt, int w, int h, int Q, int key_rate, int lmask, int cmask, int n, const void* d_frames,
                 void* d_stream, int align, uint64_t* pkt_offset, uint32_t* pkt_len) {
-  if (fmt == MI_RTJ_FMT_YUV420) {
-    if (!c || !d_frames || !d_stream || !pkt_offset || !pkt_len || w <= 0 || h <= 0 || (w & 15) || (h & 15) ||
-        n <= 0 || align < 1 || (align & (align - 1)))
-      return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: bad argument");
+  if (!format_known(fmt))
+    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: unknown format %d (0 = 4:2:0, 1 = 4:2:2, 2 = greyscale)", fmt);
+  const Format& F = kFormats[fmt];
+  const bool args_ok = c && d_frames && d_stream && pkt_offset && pkt_len && n > 0 && align >= 1 && !(align & (align - 1));
+  if (fmt == MI_RTJ_FMT_YUV420) {  // the calls without a format argument have one message for everything
+    if (!args_ok || !F.geometry_ok(w, h)) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: bad argument");
   } else {
-    if (fmt != MI_RTJ_FMT_YUV422 && fmt != MI_RTJ_FMT_GREY)
-      return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: unknown format %d (0 = 4:2:0, 1 = 4:2:2, 2 = greyscale)", fmt);
-    if (!c || !d_frames || !d_stream || !pkt_offset || !pkt_len || n <= 0 || align < 1 || (align & (align - 1)))
+    if (!args_ok)
       return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: bad argument (NULL buffer, no pictures, or align not a power of two)");
-    if (fmt == MI_RTJ_FMT_YUV422 && (w <= 0 || h <= 0 || (w & 15) || (h & 7)))
-      return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: %dx%d: a 4:2:2 picture's width is a positive multiple of 16, its height "
-                  "a positive multiple of 8", w, h);
-    if (fmt == MI_RTJ_FMT_GREY && (w <= 0 || h <= 0 || (w & 7) || (h & 7)))
-      return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: %dx%d: a greyscale picture's width and height are positive multiples of 8",
-                  w, h);
+    if (!F.geometry_ok(w, h)) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_encode: %dx%d: %s", w, h, F.encode_rule);
   }
   if (Q < 1) Q = 1;
   if (Q > 255) Q = 255;
@@ -2284,9 +2295,8 @@ int encode_impl(mi_rtj_ctx* c, int fmt, int w, int h, int Q, int key_rate, int l
   cmask = cmask < 0 ? 0 : (cmask > 16 ? 16 : cmask);
   const bool inter = key_rate > 0;
   HIPCHK(c, hipSetDevice(c->device));
-  const uint32_t nblk = fmt == MI_RTJ_FMT_YUV422 ? (uint32_t)(w / 16) * (h / 8) * 4
-                        : fmt == MI_RTJ_FMT_GREY ? (uint32_t)(w / 8) * (h / 8) : (uint32_t)(w / 16) * (h / 16) * 6;
-  const size_t fsz = fmt == MI_RTJ_FMT_YUV422 ? (size_t)w * h * 2 : fmt == MI_RTJ_FMT_GREY ? (size_t)w * h : (size_t)w * h * 3 / 2;
+  const uint32_t nblk = (uint32_t)F.blocks(w, h);
+  const size_t fsz = F.picture_bytes(w, h);
   // frames per pass: inter frames depend on each other, intra ones do not (256: 0.8 GB of block slots at 1080p)
   const int chunk = inter ? 1 : (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)1 << 30) / ((size_t)nblk * 64)));
   uint8_t *slots = nullptr, *lens = nullptr;
@@ -2329,21 +2339,11 @@ int encode_impl(mi_rtj_ctx* c, int fmt, int w, int h, int Q, int key_rate, int l
   int key_count = 0;
   for (int f0 = 0; f0 < n; f0 += chunk) {
     const int m = n - f0 < chunk ? n - f0 : chunk;
-    const size_t tot = (size_t)m * nblk;
     // RTjpeg_compress: the previous-block store is cleared whenever key_count is 0 (lib/RTjpeg.c:3504-3505)
     if (inter && key_count == 0) ENC_CHK(hipMemsetAsync(old, 0, (size_t)nblk * 64 * sizeof(int16_t), c->stream));
-    if (fmt != MI_RTJ_FMT_YUV420) {  // one wave per 64 blocks, inter pictures too (rtj_encode_fmt_kernels.h)
-      const uint8_t* fr = (const uint8_t*)d_frames + (size_t)f0 * fsz;
-      if (inter) launch_encode_fmt<true>(fmt, c->stream, fr, w, h, m, c->d_lut + Q, slots, lens, old, lmask, cmask);
-      else launch_encode_fmt<false>(fmt, c->stream, fr, w, h, m, c->d_lut + Q, slots, lens, nullptr, 0, 0);
-    } else if (inter) {
-      hipLaunchKernelGGL(k_encode_blocks, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
-                         (const uint8_t*)d_frames + (size_t)f0 * fsz, w, h, m, c->d_lut + Q, slots, lens, old, lmask, cmask);
-    } else {  // intra: a wave per 64 horizontally adjacent blocks (rtj_encode_kernels.h)
-      const unsigned groups = (nblk / 6u + (unsigned)kMbPerGroup - 1u) / (unsigned)kMbPerGroup;
-      hipLaunchKernelGGL(k_encode_wave, dim3(3u * groups, (unsigned)m), dim3(64), 0, c->stream,
-                         (const uint8_t*)d_frames + (size_t)f0 * fsz, w, h, c->d_lut + Q, slots, lens);
-    }
+    const uint8_t* fr = (const uint8_t*)d_frames + (size_t)f0 * fsz;
+    if (inter) launch_encode_fmt<true>(fmt, c->stream, fr, w, h, m, c->d_lut + Q, slots, lens, old, lmask, cmask);
+    else launch_encode_fmt<false>(fmt, c->stream, fr, w, h, m, c->d_lut + Q, slots, lens, nullptr, 0, 0);
     hipLaunchKernelGGL(k_encode_scan, dim3(m), dim3(256), 0, c->stream, lens, nblk, offs, fbytes);
     hipLaunchKernelGGL(k_encode_place, dim3(1), dim3(256), 0, c->stream, fbytes, m, (uint32_t)align, d_cursor, d_alloff + f0,
                        d_alllen + f0, d_pktoff);

@@ -48,6 +48,43 @@ constexpr int kStageN = 4096;             // bytes staged per chunk (kTabN + 64 
 
 constexpr int kMbPerGroup = 32;  // macroblocks per decode workgroup (3 waves: Ytop, Ybottom, chroma)
 
+// The three arms of RTjpeg_compress / RTjpeg_decompress (lib/RTjpeg.c:3488-3524, 3580-3585), numbered as MI_RTJ_FMT_*.
+// FmtShape is the one statement of a format's geometry: the kernels that are templates on the format read it, and the
+// host's table of formats (mi_rtjpeg.hip) is generated from it.
+//   4:2:0  macroblock 16x16: Y Y Y Y Cb Cr, chroma planes w/2 x h/2
+//   4:2:2  macroblock 16x8:  Y Y Cb Cr,     chroma planes w/2 x h
+//   grey   "macroblock" = one 8x8 block, raster order, one plane
+// A group is what one workgroup (decode) or `kParts` workgroups (encode) cover; a part is 64 blocks, one per lane:
+// a row of 64 luma blocks, or 32 Cb + 32 Cr blocks.
+enum { kFmtYUV420 = 0, kFmtYUV422 = 1, kFmtGrey = 2 };
+
+template <int Fmt>
+struct FmtShape;
+template <>
+struct FmtShape<kFmtYUV420> {
+  static constexpr uint32_t kMbW = 16, kMbH = 16;  // pixels
+  static constexpr uint32_t kBlkPerMb = 6;
+  static constexpr uint32_t kParts = 3;  // upper luma row | lower luma row | chroma
+  static constexpr uint32_t kUnitsPerGroup = (uint32_t)kMbPerGroup;
+  static constexpr uint32_t kChromaPlanes = 2, kChromaShiftX = 1, kChromaShiftY = 1;
+};
+template <>
+struct FmtShape<kFmtYUV422> {
+  static constexpr uint32_t kMbW = 16, kMbH = 8;
+  static constexpr uint32_t kBlkPerMb = 4;
+  static constexpr uint32_t kParts = 2;  // luma row | chroma
+  static constexpr uint32_t kUnitsPerGroup = (uint32_t)kMbPerGroup;
+  static constexpr uint32_t kChromaPlanes = 2, kChromaShiftX = 1, kChromaShiftY = 0;
+};
+template <>
+struct FmtShape<kFmtGrey> {
+  static constexpr uint32_t kMbW = 8, kMbH = 8;
+  static constexpr uint32_t kBlkPerMb = 1;
+  static constexpr uint32_t kParts = 1;
+  static constexpr uint32_t kUnitsPerGroup = 64;
+  static constexpr uint32_t kChromaPlanes = 0, kChromaShiftX = 0, kChromaShiftY = 0;
+};
+
 // zig-zag order of the bitstream, transposed relative to JPEG (lib/RTjpeg.c:59-74)
 #define MIRTJ_ZZ_INIT                                                                        \
   {0,  8,  1,  2,  9,  16, 24, 17, 10, 3,  4,  11, 18, 25, 32, 40, 33, 26, 19, 12, 5,  6,   \

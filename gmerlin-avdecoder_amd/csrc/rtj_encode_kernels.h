@@ -1,12 +1,15 @@
-// rtj_encode_kernels.h — gfx950 kernels of the stream generator:
-// synthetic frame content and the intra-only RTjpeg encoder (lib/RTjpeg.c:109-155, 245-252,
-// 288-389, 2510-2563, 3488-3524).  Not on the timed path: it exists so that benchmark-size
-// streams can be made on the GPU box, and as the mirror image of the decode kernels.
+// rtj_encode_kernels.h — gfx950 kernels of the stream generator: synthetic frame content and
+// the RTjpeg encoder of all three formats, intra and inter (RTjpeg_compress, lib/RTjpeg.c:3488-3524).  Not on the timed
+// path: it exists so that benchmark-size streams can be made on the GPU box, and as the mirror image of the decode kernels.
+//
+//   k_synth, k_synth_lcg     4:2:0 pictures
+//   k_encode_fmt<Fmt, kInter>  blocks -> 64-byte slots and lengths: the one kernel that knows a format
+//   k_encode_scan, k_encode_place, k_encode_pack   slots -> packets; they only know a block count
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "rtj_common.h"
-#include "rtj_decode_kernels.h"  // c_zz
+#include "rtj_decode_kernels.h"  // kMaxRawBytes
 
 namespace mirtj {
 
@@ -111,137 +114,27 @@ __device__ __forceinline__ void fdct8(const int (&p)[8], int (&r)[8]) {
   r[7] = z11 - z4;
 }
 
-// One thread per 8x8 block: DCT + quantise + run-length pack into a private 64-byte slot.
-// blocks are numbered in stream order (6 per macroblock) across all frames of the call.
-// With `old` (inter mode, RTjpeg_mcompressYUV420 lib/RTjpeg.c:2841-2921 + RTjpeg_bcomp :2827-2838) the
-// call covers ONE frame: a block whose quantised coefficients all lie within `mask` of the stored
-// previous ones is emitted as the single byte 0xFF and the store is left alone; otherwise the store
-// takes the new block.
-__global__ void k_encode_blocks(const uint8_t* __restrict__ frames, int w, int h, int nframes,
-                                const QTab* __restrict__ qt, uint8_t* __restrict__ slots,
-                                uint8_t* __restrict__ lens, int16_t* __restrict__ old, int lmask, int cmask) {
-  const uint32_t nmb = (uint32_t)(w / 16) * (h / 16), mbw = w / 16;
-  const size_t total = (size_t)nframes * nmb * 6;
-  const size_t gb = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gb >= total) return;
-  const uint32_t fr = (uint32_t)(gb / (nmb * 6u)), bi = (uint32_t)(gb % (nmb * 6u));
-  const uint32_t mb = bi / 6u, k = bi % 6u, mx = mb % mbw, my = mb / mbw;
-  const size_t ysz = (size_t)w * h;
-  const uint8_t* f = frames + (size_t)fr * (ysz + (ysz >> 1));
-  const uint8_t* src;
-  int stride;
-  if (k < 4) {
-    stride = w;
-    src = f + (size_t)(16u * my + 8u * (k >> 1)) * w + 16u * mx + 8u * (k & 1u);
-  } else {
-    stride = w >> 1;
-    src = f + ysz + (k == 5 ? ysz >> 2 : 0) + (size_t)(8u * my) * stride + 8u * mx;
-  }
-  int ws[64];
-#pragma unroll
-  for (int row = 0; row < 8; row++) {
-    int p[8], r[8];
-#pragma unroll
-    for (int c = 0; c < 8; c++) p[c] = src[(size_t)row * stride + c];
-    fdct8(p, r);
-    r[0] <<= 8;
-    r[4] <<= 8;
-#pragma unroll
-    for (int c = 0; c < 8; c++) ws[8 * row + c] = r[c];
-  }
-  const int32_t* q = k < 4 ? qt->lqt : qt->cqt;
-  int16_t blk[64];
-#pragma unroll
-  for (int c = 0; c < 8; c++) {
-    int p[8], r[8];
-#pragma unroll
-    for (int kk = 0; kk < 8; kk++) p[kk] = ws[8 * kk + c];
-    fdct8(p, r);
-#pragma unroll
-    for (int kk = 0; kk < 8; kk++) {
-      const int16_t d = (kk == 0 || kk == 4) ? (int16_t)((r[kk] + 128) >> 8) : (int16_t)((r[kk] + 32768) >> 16);
-      blk[8 * kk + c] = (int16_t)(((int)d * q[8 * kk + c] + 32767) >> 16);  // RTjpeg_quant
-    }
-  }
-  uint8_t* out = slots + gb * 64;
-  if (old) {
-    int16_t* o = old + gb * 64;
-    const int mask = k < 4 ? lmask : cmask;
-    bool same = true;
-    for (int i = 0; i < 64; i++) {
-      const int d = (int)o[i] - (int)blk[i];
-      same = same && (d < 0 ? -d : d) <= mask;
-    }
-    if (same) {
-      out[0] = 0xFF;
-      lens[gb] = 1;
-      return;
-    }
-    for (int i = 0; i < 64; i++) o[i] = blk[i];
-  }
-  // RTjpeg_b2s: DC clamped to 0..254, bt8 full-range bytes, then 7-bit values and zero runs
-  const int bt8 = k < 4 ? qt->lb8 : qt->cb8;
-  int n = 0, z = 1;
-  int v = blk[c_zz[0]];
-  out[n++] = (uint8_t)(v > 254 ? 254 : (v < 0 ? 0 : v));
-  for (; z <= bt8; z++) {
-    v = blk[c_zz[z]];
-    out[n++] = (uint8_t)(int8_t)(v > 127 ? 127 : (v < -128 ? -128 : v));
-  }
-  while (z < 64) {
-    v = blk[c_zz[z]];
-    if (v != 0) {
-      out[n++] = (uint8_t)(int8_t)(v > 63 ? 63 : (v < -64 ? -64 : v));
-      z++;
-    } else {
-      int run = 0;
-      while (z < 64 && blk[c_zz[z]] == 0) {
-        z++;
-        run++;
-      }
-      out[n++] = (uint8_t)(63 + run);
-    }
-  }
-  lens[gb] = (uint8_t)n;
-}
+// ---- the encoder's transform kernel, every format and both modes ----
+//
+//   RTjpeg_compressYUV420 / RTjpeg_mcompressYUV420 (lib/RTjpeg.c:2510-2563, 2841-2921)
+//   RTjpeg_compressYUV422 / RTjpeg_mcompressYUV422 (lib/RTjpeg.c:2565-2608, 2924-2988)
+//   RTjpeg_compress8 / RTjpeg_mcompress8           (lib/RTjpeg.c:2610-2637, 2990-3018)
+//
+// Greyscale codes the picture it is given: block (row r, column c) is lines 8r .. 8r+7, pixels 8c .. 8c+7, line stride
+// w — the picture RTjpeg_decompress8 puts back.  The reference's greyscale arms do not: they hand RTjpeg_dctY the width
+// where the other arms hand it width / 8 (lib/RTjpeg.c:2626, 3004; RTjpeg_dctY advances by rskip << 3, :341), so a block is
+// read with a line stride of 8 w, and the intra arm moves on by ONE line per block row (:2630).  Everything else of a
+// greyscale block's coding is the luma block's of the other formats, which are held to the reference.
 
-// The intra form, one WAVE per 64 horizontally adjacent blocks (the arrangement of k_decode: a macroblock group of 32
-// macroblocks has three parts — upper luma, lower luma, chroma — and a lane holds one block of its part), round 4:
-//   * a lane reads its block as eight 8-byte pieces of rows that the wave's lanes cover contiguously (k_encode_blocks
-//     reads byte by byte, one thread per block in stream order);
-//   * both transform passes and the quantiser in registers, every index a compile-time constant;
-//   * the run-length pack walks the zig-zag order fully unrolled (the coefficient of a slot is a REGISTER, not an
-//     indexed array in scratch memory) and appends bytes to the lane's 64-byte slot in LDS under lane predicates;
-//   * the slot leaves as four 16-byte stores.
-// Same arithmetic, same bytes (lib/RTjpeg.c:288-389 dctY, :245-252 quant, :109-155 b2s).  grid (3 * groups, frames).
-constexpr int kEncSlotStride = 80;  // LDS bytes per lane: a 64-byte slot + padding (16-byte reads without bank conflicts)
-__global__ __launch_bounds__(64) void k_encode_wave(const uint8_t* __restrict__ frames, int w, int h,
-                                                     const QTab* __restrict__ qt, uint8_t* __restrict__ slots,
-                                                     uint8_t* __restrict__ lens) {
-  __shared__ __attribute__((aligned(16))) uint8_t s_slot[64 * kEncSlotStride];
-  const int lane = threadIdx.x;
-  const uint32_t mbw = (uint32_t)w / 16u, nmb = mbw * ((uint32_t)h / 16u);
-  const uint32_t grp = blockIdx.x / 3u, part = blockIdx.x - 3u * grp, fr = blockIdx.y;
-  const uint32_t dmb = part == 2u ? (uint32_t)(lane & 31) : (uint32_t)(lane >> 1);
-  const uint32_t k = part == 2u ? 4u + (uint32_t)(lane >> 5) : 2u * part + (uint32_t)(lane & 1);
-  const uint32_t mb = grp * (uint32_t)kMbPerGroup + dmb;
-  if (mb >= nmb) return;  // (no barrier below: a wave's lanes only touch their own slots)
-  const uint32_t my = mb / mbw, mx = mb - my * mbw;
-  const size_t ysz = (size_t)w * h;
-  const uint8_t* f = frames + (size_t)fr * (ysz + (ysz >> 1));
-  const uint8_t* src;
-  uint32_t stride;
-  if (k < 4u) {
-    stride = (uint32_t)w;
-    src = f + (size_t)(16u * my + 8u * (k >> 1)) * w + 16u * mx + 8u * (k & 1u);
-  } else {
-    stride = (uint32_t)w >> 1;
-    src = f + ysz + (k == 5u ? ysz >> 2 : 0) + (size_t)(8u * my) * stride + 8u * mx;
-  }
+// Rows -> quantised coefficients in natural order (lib/RTjpeg.c:288-389 dctY, :245-252 quant): eight 8-byte row loads
+// (aligned: a block starts at a multiple of 8 pixels of a line whose stride is a multiple of 8), both passes and the
+// quantiser in registers, every index a compile-time constant.
+__device__ __forceinline__ void encode_block_transform(const uint8_t* __restrict__ src, uint32_t stride,
+                                                 const int32_t* __restrict__ q, int (&blk)[64]) {
   int ws[64];
 #pragma unroll
   for (int row = 0; row < 8; row++) {
-    const uint2 d = *(const uint2*)(src + (size_t)row * stride);  // 8-byte aligned: widths are multiples of 16
+    const uint2 d = *(const uint2*)(src + (size_t)row * stride);
     int p[8] = {(int)(d.x & 255u), (int)((d.x >> 8) & 255u), (int)((d.x >> 16) & 255u), (int)(d.x >> 24),
                 (int)(d.y & 255u), (int)((d.y >> 8) & 255u), (int)((d.y >> 16) & 255u), (int)(d.y >> 24)};
     int r[8];
@@ -251,8 +144,6 @@ __global__ __launch_bounds__(64) void k_encode_wave(const uint8_t* __restrict__ 
 #pragma unroll
     for (int c = 0; c < 8; c++) ws[8 * row + c] = r[c];
   }
-  const int32_t* q = k < 4u ? qt->lqt : qt->cqt;
-  int blk[64];
 #pragma unroll
   for (int c = 0; c < 8; c++) {
     int p[8], r[8];
@@ -265,10 +156,14 @@ __global__ __launch_bounds__(64) void k_encode_wave(const uint8_t* __restrict__ 
       blk[8 * kk + c] = (int)(int16_t)(((int)d * q[8 * kk + c] + 32767) >> 16);  // RTjpeg_quant
     }
   }
-  // RTjpeg_b2s: DC clamped to 0..254, bt8 full-range bytes, then 7-bit values and zero runs (63 + run)
+}
+
+// RTjpeg_b2s (lib/RTjpeg.c:109-155) into the lane's LDS slot: DC clamped to 0..254, bt8 full-range bytes, then 7-bit
+// values and zero runs (63 + run); the zig-zag order fully unrolled, so that the coefficient of a slot is a register,
+// not an indexed array in scratch memory.  Returns the block's length, 2..64.
+constexpr int kEncSlotStride = 80;  // LDS bytes per lane: a 64-byte slot + padding (16-byte reads without bank conflicts)
+__device__ __forceinline__ int encode_block_pack(const int (&blk)[64], int bt8, uint8_t* out) {
   constexpr uint8_t zz[64] = MIRTJ_ZZ_INIT;
-  const int bt8 = k < 4u ? qt->lb8 : qt->cb8;  // the same for all lanes of a part
-  uint8_t* const out = s_slot + lane * kEncSlotStride;
   int n = 0, run = 0;
   {
     const int v = blk[zz[0]];
@@ -290,12 +185,95 @@ __global__ __launch_bounds__(64) void k_encode_wave(const uint8_t* __restrict__ 
     }
   }
   if (run) out[n++] = (uint8_t)(63 + run);
-  const size_t gb = (size_t)fr * nmb * 6u + 6u * mb + k;
+  return n;
+}
+
+// k_encode_fmt<Fmt, kInter>: forward transform + quantiser + run-length pack, one lane per 8x8 block, one wave per part of
+// a group (FmtShape, rtj_common.h; the lane arrangement of k_decode and k_decode_fmt).  grid (parts * groups, pictures),
+// one wave per workgroup.
+//   4:2:0, 4:2:2  group = kMbPerGroup consecutive macroblocks.  A luma part is one row of their luma blocks (4:2:0 has
+//          two, the upper and the lower): lane l has block 2 * part + (l & 1) of macroblock l >> 1, so a row load of the
+//          wave covers 512 contiguous pixels (or two or more stretches where the group wraps a picture row).  The last
+//          part is chroma: lanes 0-31 the Cb blocks, lanes 32-63 the Cr blocks, the macroblock's last two.
+//   grey   group = 64 consecutive blocks in raster order.
+// A lane divides its own macroblock (block) number by the count per picture row, so a group that wraps picture rows is
+// no special case; lanes past the picture's last block return before their first load.  No barrier anywhere: a lane
+// only touches its own LDS slot.
+// Blocks are numbered in stream order across the pictures of the call: slot, length and (kInter) previous-block entry
+// of block b of picture p are at p * nblk + b.
+// kInter (RTjpeg_bcomp, lib/RTjpeg.c:2827-2838; one picture per launch, in stream order): `old` holds int16[64] per
+// block, natural coefficient order.  A block whose 64 quantised coefficients all lie within the mask (lmask / cmask by
+// block type) of its entry becomes the single byte 0xFF and leaves the entry alone; otherwise the entry takes the whole
+// new block and the block is coded.
+template <int Fmt, bool kInter>
+__global__ __launch_bounds__(64) void k_encode_fmt(const uint8_t* __restrict__ frames, int w, int h,
+                                                const QTab* __restrict__ qt, uint8_t* __restrict__ slots,
+                                                uint8_t* __restrict__ lens, int16_t* __restrict__ old, int lmask,
+                                                int cmask) {
+  using S = FmtShape<Fmt>;
+  __shared__ __attribute__((aligned(16))) uint8_t s_slot[64 * kEncSlotStride];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t mbw = (uint32_t)w / S::kMbW, nmb = mbw * ((uint32_t)h / S::kMbH);
+  const uint32_t grp = blockIdx.x / S::kParts, part = blockIdx.x - grp * S::kParts, fr = blockIdx.y;  // wave-uniform
+  const bool chroma = S::kChromaPlanes != 0 && part == S::kParts - 1u;
+  const uint32_t lrow = S::kMbH > 8u ? part : 0u;  // a luma part's row of blocks in its macroblocks
+  uint32_t unit, kblk;  // macroblock (grey: block) of the picture, block of the macroblock
+  if (S::kBlkPerMb > 1) {
+    unit = grp * S::kUnitsPerGroup + (chroma ? (lane & 31u) : (lane >> 1));
+    kblk = chroma ? S::kBlkPerMb - 2u + (lane >> 5) : 2u * lrow + (lane & 1u);
+  } else {
+    unit = grp * S::kUnitsPerGroup + lane;
+    kblk = 0u;
+  }
+  if (unit >= nmb) return;
+  const uint32_t uy = unit / mbw, ux = unit - uy * mbw;
+  const size_t ysz = (size_t)w * h, csz = ysz >> (S::kChromaShiftX + S::kChromaShiftY);
+  const uint8_t* f = frames + (size_t)fr * (ysz + S::kChromaPlanes * csz);
+  const uint8_t* src;
+  uint32_t stride;
+  if (chroma) {
+    stride = (uint32_t)w >> S::kChromaShiftX;
+    src = f + ysz + (lane >> 5 ? csz : (size_t)0) + (size_t)(8u * uy) * stride + 8u * ux;
+  } else {
+    stride = (uint32_t)w;
+    src = f + (size_t)(S::kMbH * uy + 8u * lrow) * stride + S::kMbW * ux + 8u * (kblk & 1u);
+  }
+  int blk[64];
+  encode_block_transform(src, stride, chroma ? qt->cqt : qt->lqt, blk);
+  const size_t gb = (size_t)fr * nmb * S::kBlkPerMb + S::kBlkPerMb * unit + kblk;
+  if (kInter) {
+    uint4* o4 = (uint4*)(old + gb * 64);  // 128 bytes per block: 16-byte aligned
+    const int mask = chroma ? cmask : lmask;
+    bool same = true;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const uint4 o = o4[i];
+      const uint32_t wv[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int d0 = (int)(int16_t)(wv[j] & 0xFFFFu) - blk[8 * i + 2 * j];
+        const int d1 = ((int)wv[j] >> 16) - blk[8 * i + 2 * j + 1];
+        same = same && (d0 < 0 ? -d0 : d0) <= mask && (d1 < 0 ? -d1 : d1) <= mask;
+      }
+    }
+    if (same) {
+      slots[gb * 64] = 0xFF;
+      lens[gb] = 1;
+      return;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      auto pk = [&](int a) { return ((uint32_t)blk[a] & 0xFFFFu) | ((uint32_t)blk[a + 1] << 16); };
+      o4[i] = make_uint4(pk(8 * i), pk(8 * i + 2), pk(8 * i + 4), pk(8 * i + 6));
+    }
+  }
+  uint8_t* const out = s_slot + lane * kEncSlotStride;
+  const int n = encode_block_pack(blk, chroma ? qt->cb8 : qt->lb8, out);  // (the tables are the same for all lanes of a part)
   lens[gb] = (uint8_t)n;
-  const uint4* o4 = (const uint4*)out;
+  const uint4* s4 = (const uint4*)out;
   uint4* g4 = (uint4*)(slots + gb * 64);
 #pragma unroll
-  for (int i = 0; i < 4; i++) g4[i] = o4[i];
+  for (int i = 0; i < 4; i++) g4[i] = s4[i];
 }
 
 // Where the packets of a pass go: frame sizes (k_encode_scan) -> packet offsets in the output stream, each aligned to

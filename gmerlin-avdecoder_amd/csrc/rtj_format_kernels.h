@@ -22,27 +22,6 @@
 
 namespace mirtj {
 
-enum { kFmtYUV420 = 0, kFmtYUV422 = 1, kFmtGrey = 2 };
-
-template <int Fmt>
-struct FmtShape;
-template <>
-struct FmtShape<kFmtYUV422> {
-  static constexpr uint32_t kBlkPerMb = 4;  // Y Y Cb Cr
-  static constexpr uint32_t kParts = 2;     // of a group of kMbPerGroup macroblocks: 64 luma blocks | 32 Cb + 32 Cr
-  static constexpr uint32_t kUnitsPerGroup = (uint32_t)kMbPerGroup;
-};
-template <>
-struct FmtShape<kFmtGrey> {
-  static constexpr uint32_t kBlkPerMb = 1;
-  static constexpr uint32_t kParts = 1;  // a group is 64 consecutive blocks in raster order
-  static constexpr uint32_t kUnitsPerGroup = 64;
-};
-
-__host__ __device__ constexpr uint32_t fmt_blocks_per_mb(int fmt) { return fmt == kFmtYUV422 ? 4u : fmt == kFmtGrey ? 1u : 6u; }
-__host__ __device__ constexpr uint32_t fmt_units_per_group(int fmt) { return fmt == kFmtGrey ? 64u : (uint32_t)kMbPerGroup; }
-__host__ __device__ constexpr uint32_t fmt_parts(int fmt) { return fmt == kFmtYUV422 ? 2u : fmt == kFmtGrey ? 1u : 3u; }
-
 // ---------------------------------------------------------------------------------------
 // walk_packet_fmt: walk_packet (rtj_decode_kernels.h:214-294) for the format's macroblock.  One wave, the position in
 // scalar registers, both windows searched at once, one straight path per block; the macroblock's blocks are unrolled

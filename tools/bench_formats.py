@@ -19,8 +19,8 @@ Printed per format: pictures per second from wall time over --steps launches aft
 transform's device time per launch (mi_rtj_plan_times: MI_RTJ_K_EMIT, MI_RTJ_K_DECODE; for 4:2:0 every kernel of its
 path), the algorithmic bytes (packets read once, planes written once) and the transform's share of 8 TB/s with them; and
 "encoder": pictures and blocks per second of one intra call over --enc-frames resident pictures (wall time of the
-synchronous call, the median of five after one warm-up call).  The encoder's yardstick is the 4:2:0 figure of the same run
-(k_encode_wave): the formats run the same work per block on 4/3 and 2/3 of the blocks.
+synchronous call, the median of five after one warm-up call).  The encoder's yardstick is the 4:2:0 call of the same run
+(mi_rtj_encode_frames): the formats run the same kernel and the same work per block on 4/3 and 2/3 of the blocks.
 There is no pass mark: these formats have no earlier figure.  Prints one JSON line."""
 import argparse
 import importlib
@@ -189,7 +189,7 @@ def main():
         res[NAMES[fmt]] = measure(P, F, R, fmt, a.width, a.height, a.frames, a.distinct, a.steps, a.warmup, a.packets,
                                   a.enc_frames)
     base = res[NAMES[F.FMT_420]]["encoder"]
-    for fmt in (F.FMT_422, F.FMT_GREY):  # the yardstick: k_encode_wave's rate per block in the same run
+    for fmt in (F.FMT_422, F.FMT_GREY):  # the yardstick: the 4:2:0 call's rate per block in the same run
         e = res[NAMES[fmt]]["encoder"]
         if e and base:
             e["yuv420_pictures_per_s_same_run"] = base["pictures_per_s"]
