@@ -58,6 +58,21 @@ constexpr int kSegments = 270;  // video segments per frame: 10 DIF sequences of
     (y8) = (x32) > 21u ? 2u * serp_ + 6u * i_ : serp_ + 6u * i_;                              \
   } while (0)
 #define MIDV_PLACE_525(seq, slot, m, x32, y8) MIDV_PLACE_411(10u, seq, slot, m, x32, y8)
+
+// What a macroblock covers of a picture: one rectangle in each plane (Y, Cb, Cr), in that plane's own pixels.  rects()
+// of a system, beside its place(), gives the three for macroblock m of segment `slot` of sequence `seq`; the numbers are
+// those of k_dv_decode's store section (which does not call it: dv_decode_kernels.h).  The hold pass (dv_hold_kernels.h)
+// and mi_dv_mb_rects both call it.
+struct Rect {
+  uint32_t x, y, w, h;
+};
+// 4:1:1 at (x32, y8): 32 x 8 with one 8 x 8 chroma block in each plane; in column 22 16 x 16, and the chroma block's two
+// 4-wide halves lie one above the other
+MIDV_HD void rects_411(uint32_t x32, uint32_t y8, Rect r[3]) {
+  const bool edge = x32 == 22u;
+  r[0] = edge ? Rect{704u, 8u * y8, 16u, 16u} : Rect{32u * x32, 8u * y8, 32u, 8u};
+  r[1] = r[2] = edge ? Rect{176u, 8u * y8, 4u, 16u} : Rect{8u * x32, 8u * y8, 8u, 8u};
+}
 struct Sys525 {
   static constexpr int kId = 0, kChans = 1;
   static constexpr bool k411 = true;  // 32 x 8 macroblocks, 16 x 16 with split chroma blocks in column 22
@@ -65,6 +80,11 @@ struct Sys525 {
   static constexpr int kW = 720, kH = 480, kCW = 180, kCH = 480, kPicBytes = kW * kH + 2 * kCW * kCH;
   static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x32, uint32_t& y8) {
     MIDV_PLACE_525(seq, slot, m, x32, y8);
+  }
+  static MIDV_HD void rects(uint32_t seq, uint32_t slot, uint32_t m, Rect r[3]) {
+    uint32_t x32, y8;
+    place(seq, slot, m, x32, y8);
+    rects_411(x32, y8, r);
   }
 };
 
@@ -85,6 +105,12 @@ struct Sys625 {
     x16 = 9u * col + c;
     y16 = 3u * row + (c & 1u ? 2u - r : r);
   }
+  static MIDV_HD void rects(uint32_t seq, uint32_t slot, uint32_t m, Rect r[3]) {
+    uint32_t x16, y16;
+    place(seq, slot, m, x16, y16);
+    r[0] = Rect{16u * x16, 16u * y16, 16u, 16u};
+    r[1] = r[2] = Rect{8u * x16, 8u * y16, 8u, 8u};
+  }
 };
 
 // 625/50 4:1:1 ("DVCPRO" 25 Mbit/s PAL: DSF 1, VAUX stype 0, APT != 0; lib/dvframe.c:149-169; SMPTE 314M as this
@@ -98,6 +124,11 @@ struct Sys625_411 {
   static constexpr int kW = 720, kH = 576, kCW = 180, kCH = 576, kPicBytes = kW * kH + 2 * kCW * kCH;
   static MIDV_HD void place(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x32, uint32_t& y8) {
     MIDV_PLACE_411(12u, seq, slot, m, x32, y8);
+  }
+  static MIDV_HD void rects(uint32_t seq, uint32_t slot, uint32_t m, Rect r[3]) {
+    uint32_t x32, y8;
+    place(seq, slot, m, x32, y8);
+    rects_411(x32, y8, r);
   }
 };
 
@@ -122,6 +153,12 @@ struct Sys422 {
     const uint32_t c = slot / 3u, r = slot - 3u * c;
     x16 = 9u * col + c;
     y8 = 3u * (2u * row + chan) + (c & 1u ? 2u - r : r);
+  }
+  static MIDV_HD void rects(uint32_t seq, uint32_t slot, uint32_t m, Rect r[3]) {  // (`seq` as place() takes it)
+    uint32_t x16, y8;
+    place(seq, slot, m, x16, y8);
+    r[0] = Rect{16u * x16, 8u * y8, 16u, 8u};
+    r[1] = r[2] = Rect{8u * x16, 8u * y8, 8u, 8u};
   }
 };
 using Sys525_422 = Sys422<4, 10>;  // 240,000-byte frames, 720 x 480

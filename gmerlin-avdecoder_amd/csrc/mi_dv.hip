@@ -13,6 +13,7 @@
 #include "../../include/mi_dv.h"
 #include "dv_common.h"
 #include "dv_decode_kernels.h"
+#include "dv_hold_kernels.h"
 
 using namespace midv;
 
@@ -48,6 +49,24 @@ struct mi_dv_ctx {
   uint8_t* d_pic = nullptr;
   uint8_t* h_pic = nullptr;  // pinned
   size_t cap_frame = 0, cap_pic = 0;
+  // the held calls (mi_dv_decode_batch_held, mi_dv_decode_frame_held).  Everything only grows.
+  struct Hold {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_used;  // one pair around every phase 2 since the last mi_dv_hold_times
+    uint8_t* h_desc = nullptr;                               // pinned: the chunks, then the runs, of the last batch
+    uint8_t* d_desc = nullptr;
+    size_t cap_desc = 0;
+    hipEvent_t desc_done = nullptr;  // behind the last upload of h_desc
+    uint64_t* d_mask = nullptr;      // [chunk][macroblock]
+    int32_t* d_carry = nullptr;
+    size_t cap_rows = 0;
+    unsigned long long* d_held = nullptr;  // kHoldCounters partial counts
+    bool counted = false;  // the last held batch ran phase 2: d_held is its count (else the count is 0)
+    // the one-frame path: per system the last picture and the one being made, in turns; the system whose keep[][cur] is
+    // the picture of the frame decoded last (-1: none; the next frame has no source)
+    uint8_t* keep[6][2] = {};
+    int cur[6] = {};
+    int kept = -1;
+  } hold;
   std::string err;
 };
 
@@ -130,7 +149,14 @@ void mi_dv_destroy(mi_dv_ctx* c) {
   if (c->d_frame) (void)hipFree(c->d_frame);
   if (c->d_pic) (void)hipFree(c->d_pic);
   if (c->h_pic) (void)hipHostFree(c->h_pic);
-  for (auto* v : {&c->ev_used, &c->ev_free})
+  if (c->hold.h_desc) (void)hipHostFree(c->hold.h_desc);
+  for (void* d : {(void*)c->hold.d_desc, (void*)c->hold.d_mask, (void*)c->hold.d_carry, (void*)c->hold.d_held})
+    if (d) (void)hipFree(d);
+  for (auto& k : c->hold.keep)
+    for (uint8_t* d : k)
+      if (d) (void)hipFree(d);
+  if (c->hold.desc_done) (void)hipEventDestroy(c->hold.desc_done);
+  for (auto* v : {&c->ev_used, &c->ev_free, &c->hold.ev_used})
     for (auto& e : *v) {
       (void)hipEventDestroy(e.first);
       (void)hipEventDestroy(e.second);
@@ -245,6 +271,11 @@ struct Row {
   bool says_apt;
   int (*launch)(mi_dv_ctx*, const char*, const void*, int, void*);
   void (*place)(uint32_t, uint32_t, uint32_t, uint32_t&, uint32_t&);
+  // the held calls: macroblocks per frame, a macroblock's three rectangles, the launch of k_dv_hold_copy<Sys>
+  int nmb;
+  void (*rects)(uint32_t, uint32_t, uint32_t, Rect*);
+  void (*hold_copy)(hipStream_t, const HoldChunkDev*, uint32_t, const uint64_t*, const int32_t*, uint8_t*, const uint8_t*,
+                    unsigned long long*);
 };
 // a host function of its own: the kernels' S::place stays what dv_common.h makes of it
 template <class S>
@@ -252,9 +283,20 @@ void place_thunk(uint32_t seq, uint32_t slot, uint32_t m, uint32_t& x, uint32_t&
   S::place(seq, slot, m, x, y);
 }
 template <class S>
+void rects_thunk(uint32_t seq, uint32_t slot, uint32_t m, Rect* r) {
+  S::rects(seq, slot, m, r);
+}
+// one workgroup per (super block, kHoldSub pictures of a chunk); past 65535 items the kernel strides
+template <class S>
+void hold_copy_launch(hipStream_t st, const HoldChunkDev* chunks, uint32_t nitems, const uint64_t* mask, const int32_t* carry,
+                      uint8_t* pics, const uint8_t* prev, unsigned long long* held) {
+  hipLaunchKernelGGL(k_dv_hold_copy<S>, dim3((unsigned)(S::kChans * S::kSeqs * 5), nitems < kHoldMaxGridY ? nitems : kHoldMaxGridY),
+                     dim3(kHoldCopyThreads), 0, st, chunks, nitems, mask, carry, pics, prev, held);
+}
+template <class S>
 constexpr Row row(const char* frames, const char* what, bool says_apt, const char* expected) {
   return {S::kId, S::kFrameBytes, S::kPicBytes, {S::kW, S::kCW, S::kCW}, {S::kH, S::kCH, S::kCH}, S::kChans * S::kSeqs,
-          frames, what, expected, says_apt, launch<S>, place_thunk<S>};
+          frames, what, expected, says_apt, launch<S>, place_thunk<S>, S::kSegments * 5, rects_thunk<S>, hold_copy_launch<S>};
 }
 constexpr Row kSystems[] = {
     row<Sys525>("525/60", "525/60 25 Mbit/s DV frame", false, ""),
@@ -281,10 +323,9 @@ int classify(const uint8_t* frame, size_t len) {
   return len >= (size_t)find(system)->frame_bytes ? system : -1;
 }
 
-// one host frame of system r, checked (arguments, length, announcement: in this order), through the kernel into the
-// caller's planes
-int decode_one(mi_dv_ctx* c, const Row& r, const char* who, const uint8_t* frame, size_t len, uint8_t* const planes[3],
-               const int strides[3]) {
+// one host frame of system r, checked: arguments, length, announcement, strides, in this order
+int check_one(mi_dv_ctx* c, const Row& r, const char* who, const uint8_t* frame, size_t len, uint8_t* const planes[3],
+              const int strides[3]) {
   if (!c || !frame || !planes || !strides || !planes[0] || !planes[1] || !planes[2])
     return fail(c, MI_DV_ERR_ARG, "%s: NULL argument", who);
   if (len < (size_t)r.frame_bytes)
@@ -297,13 +338,12 @@ int decode_one(mi_dv_ctx* c, const Row& r, const char* who, const uint8_t* frame
     return fail(c, MI_DV_ERR_FORMAT, "not a %s (%s%s)", r.what, seen, r.expected);
   }
   if (strides[0] < r.w[0] || strides[1] < r.w[1] || strides[2] < r.w[2]) return fail(c, MI_DV_ERR_ARG, "strides below the picture's width");
-  DVCHK(c, hipSetDevice(c->device));
-  int rc = one_frame_buffers(c, (size_t)r.frame_bytes, (size_t)r.pic_bytes);
-  if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, (size_t)r.frame_bytes, hipMemcpyHostToDevice, c->stream));
-  rc = r.launch(c, who, c->d_frame, 1, c->d_pic);
-  if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipMemcpyAsync(c->h_pic, c->d_pic, (size_t)r.pic_bytes, hipMemcpyDeviceToHost, c->stream));
+  return MI_DV_OK;
+}
+
+// the device picture d_pic of system r through the pinned buffer into the caller's planes; synchronises
+int planes_out(mi_dv_ctx* c, const Row& r, const uint8_t* d_pic, uint8_t* const planes[3], const int strides[3]) {
+  DVCHK(c, hipMemcpyAsync(c->h_pic, d_pic, (size_t)r.pic_bytes, hipMemcpyDeviceToHost, c->stream));
   DVCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* src = c->h_pic;
   for (int pl = 0; pl < 3; pl++) {
@@ -311,6 +351,137 @@ int decode_one(mi_dv_ctx* c, const Row& r, const char* who, const uint8_t* frame
     for (int y = 0; y < h; y++) memcpy(planes[pl] + (size_t)y * strides[pl], src + (size_t)y * w, (size_t)w);
     src += (size_t)w * h;
   }
+  return MI_DV_OK;
+}
+
+// one host frame of system r, checked, through the kernel into the caller's planes
+int decode_one(mi_dv_ctx* c, const Row& r, const char* who, const uint8_t* frame, size_t len, uint8_t* const planes[3],
+               const int strides[3]) {
+  int rc = check_one(c, r, who, frame, len, planes, strides);
+  if (rc != MI_DV_OK) return rc;
+  DVCHK(c, hipSetDevice(c->device));
+  rc = one_frame_buffers(c, (size_t)r.frame_bytes, (size_t)r.pic_bytes);
+  if (rc != MI_DV_OK) return rc;
+  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, (size_t)r.frame_bytes, hipMemcpyHostToDevice, c->stream));
+  rc = r.launch(c, who, c->d_frame, 1, c->d_pic);
+  if (rc != MI_DV_OK) return rc;
+  return planes_out(c, r, c->d_pic, planes, strides);
+}
+
+// ---- the held calls ----
+// room for `desc` bytes of descriptors and `rows` mask / carry entries (they only grow; growing waits for the stream)
+int hold_buffers(mi_dv_ctx* c, size_t desc, size_t rows) {
+  mi_dv_ctx::Hold& h = c->hold;
+  if (!h.d_held) DVCHK(c, hipMalloc((void**)&h.d_held, kHoldCounters * kHoldCounterStride * sizeof(unsigned long long)));
+  if (!h.desc_done) DVCHK(c, hipEventCreateWithFlags(&h.desc_done, hipEventDisableTiming));
+  if (desc > h.cap_desc) {
+    DVCHK(c, hipStreamSynchronize(c->stream));
+    if (h.h_desc) DVCHK(c, hipHostFree(h.h_desc));
+    if (h.d_desc) DVCHK(c, hipFree(h.d_desc));
+    h.h_desc = h.d_desc = nullptr;
+    h.cap_desc = 0;
+    DVCHK(c, hipHostMalloc((void**)&h.h_desc, desc, hipHostMallocDefault));
+    DVCHK(c, hipMalloc((void**)&h.d_desc, desc));
+    h.cap_desc = desc;
+  }
+  if (rows > h.cap_rows) {
+    DVCHK(c, hipStreamSynchronize(c->stream));
+    if (h.d_mask) DVCHK(c, hipFree(h.d_mask));
+    if (h.d_carry) DVCHK(c, hipFree(h.d_carry));
+    h.d_mask = nullptr;
+    h.d_carry = nullptr;
+    h.cap_rows = 0;
+    if (hipMalloc((void**)&h.d_mask, rows * sizeof(uint64_t)) != hipSuccess || hipMalloc((void**)&h.d_carry, rows * sizeof(int32_t)) != hipSuccess)
+      return fail(c, MI_DV_ERR_NOMEM, "mi_dv_decode_batch_held: no device memory for %zu mask entries", rows);
+    h.cap_rows = rows;
+  }
+  return MI_DV_OK;
+}
+
+void hold_forget(mi_dv_ctx* c) {
+  if (c) c->hold.kept = -1;
+}
+
+// phase 1 (k_dv_decode over all n frames), then phase 2 for the runs that have a source: every argument is checked
+// before anything is launched
+int decode_held(mi_dv_ctx* c, const Row& r, const char* who, const void* d_frames, int n, void* d_pics, int n_runs,
+                const int* run_len, const void* d_prev, unsigned sta_mask) {
+  if (sta_mask > 0xFFFFu) return fail(c, MI_DV_ERR_ARG, "%s: STA mask 0x%x: one bit per STA value, at most 0xFFFF", who, sta_mask);
+  if (!d_frames || !d_pics || n <= 0 || n_runs < 0) return fail(c, MI_DV_ERR_ARG, "%s: bad argument", who);
+  if (n > 65535) return fail(c, MI_DV_ERR_ARG, "%s: %d frames; at most 65535 per call (split the batch)", who, n);
+  if (((uintptr_t)d_frames & 3u) || ((uintptr_t)d_pics & 7u) || ((uintptr_t)d_prev & 7u))
+    return fail(c, MI_DV_ERR_ARG, "%s: d_frames must be 4-byte, d_pics and d_prev 8-byte aligned", who);
+  if (n_runs == 0 || !run_len) {  // one run
+    n_runs = 1;
+    run_len = &n;
+  }
+  long long sum = 0;
+  for (int i = 0; i < n_runs; i++) {
+    if (run_len[i] <= 0) return fail(c, MI_DV_ERR_ARG, "%s: run %d has %d frames", who, i, run_len[i]);
+    sum += run_len[i];
+  }
+  if (sum != n) return fail(c, MI_DV_ERR_ARG, "%s: the %d runs hold %lld frames, the batch %d", who, n_runs, sum, n);
+  if (d_prev) {
+    const uintptr_t p0 = (uintptr_t)d_prev, p1 = p0 + (size_t)n_runs * r.pic_bytes, q0 = (uintptr_t)d_pics, q1 = q0 + (size_t)n * r.pic_bytes;
+    if (p0 < q1 && q0 < p1) return fail(c, MI_DV_ERR_ARG, "%s: d_prev overlaps d_pics", who);
+  }
+  if (!c) return fail(c, MI_DV_ERR_ARG, "%s: NULL instance", who);
+  if (!sta_mask) sta_mask = MI_DV_STA_ERRORS;
+  DVCHK(c, hipSetDevice(c->device));
+  mi_dv_ctx::Hold& h = c->hold;
+  // a run has a source when it has an earlier picture of its own or one of d_prev
+  std::vector<HoldChunkDev> chunks;
+  std::vector<HoldRunDev> runs;
+  uint32_t frame0 = 0;
+  for (int i = 0; i < n_runs; i++) {
+    const uint32_t len = (uint32_t)run_len[i];
+    if (len >= 2u || d_prev) {
+      runs.push_back({(uint32_t)chunks.size(), (len + kHoldChunk - 1u) / kHoldChunk});
+      for (uint32_t rel = 0; rel < len; rel += kHoldChunk)
+        chunks.push_back({frame0, rel, len - rel < (uint32_t)kHoldChunk ? len - rel : (uint32_t)kHoldChunk, (uint32_t)i});
+    }
+    frame0 += len;
+  }
+  const size_t chunk_bytes = chunks.size() * sizeof(HoldChunkDev), run_bytes = runs.size() * sizeof(HoldRunDev);
+  if (!chunks.empty()) {
+    const int rc = hold_buffers(c, chunk_bytes + run_bytes, chunks.size() * (size_t)r.nmb);
+    if (rc != MI_DV_OK) return rc;
+  }
+  int rc = r.launch(c, who, d_frames, n, d_pics);
+  if (rc != MI_DV_OK) return rc;
+  h.counted = false;
+  if (chunks.empty()) return MI_DV_OK;
+  DVCHK(c, hipEventSynchronize(h.desc_done));  // (the last upload has left the pinned buffer; at once if there was none)
+  memcpy(h.h_desc, chunks.data(), chunk_bytes);
+  memcpy(h.h_desc + chunk_bytes, runs.data(), run_bytes);
+  DVCHK(c, hipMemcpyAsync(h.d_desc, h.h_desc, chunk_bytes + run_bytes, hipMemcpyHostToDevice, c->stream));
+  DVCHK(c, hipEventRecord(h.desc_done, c->stream));
+  std::pair<hipEvent_t, hipEvent_t> ev;
+  if (!c->ev_free.empty()) {
+    ev = c->ev_free.back();
+    c->ev_free.pop_back();
+  } else {
+    DVCHK(c, hipEventCreate(&ev.first));
+    DVCHK(c, hipEventCreate(&ev.second));
+  }
+  h.ev_used.push_back(ev);
+  if (h.ev_used.size() > 4096) {  // nobody asks for times: keep the newest
+    c->ev_free.push_back(h.ev_used.front());
+    h.ev_used.erase(h.ev_used.begin());
+  }
+  const HoldChunkDev* d_chunks = (const HoldChunkDev*)h.d_desc;
+  const HoldRunDev* d_runs = (const HoldRunDev*)(h.d_desc + chunk_bytes);
+  const uint32_t nchunks = (uint32_t)chunks.size(), nruns = (uint32_t)runs.size(), nmb = (uint32_t)r.nmb;
+  const unsigned gx = (nmb + kHoldScanThreads - 1) / kHoldScanThreads;
+  DVCHK(c, hipEventRecord(ev.first, c->stream));
+  hipLaunchKernelGGL(k_dv_hold_mask, dim3((nmb + kHoldMaskMbs - 1u) / kHoldMaskMbs, nchunks < kHoldMaxGridY ? nchunks : kHoldMaxGridY), dim3(kHoldScanThreads), 0, c->stream,
+                     (const uint8_t*)d_frames, (uint32_t)r.frame_bytes, nmb, d_chunks, nchunks, (uint32_t)sta_mask, h.d_mask);
+  hipLaunchKernelGGL(k_dv_hold_carry, dim3(gx, nruns < kHoldMaxGridY ? nruns : kHoldMaxGridY), dim3(kHoldScanThreads), 0, c->stream,
+                     d_runs, nruns, d_chunks, nmb, (const uint64_t*)h.d_mask, h.d_carry, h.d_held);
+  r.hold_copy(c->stream, d_chunks, nchunks * (uint32_t)kHoldSubs, h.d_mask, h.d_carry, (uint8_t*)d_pics, (const uint8_t*)d_prev, h.d_held);
+  DVCHK(c, hipGetLastError());
+  DVCHK(c, hipEventRecord(ev.second, c->stream));
+  h.counted = true;
   return MI_DV_OK;
 }
 }  // namespace
@@ -384,6 +555,120 @@ int mi_dv_mb_place(int system, int seq, int slot, int m, int* x, int* y) {
   r->place((uint32_t)seq, (uint32_t)slot, (uint32_t)m, ux, uy);
   *x = (int)ux;
   *y = (int)uy;
+  return MI_DV_OK;
+}
+
+// ---- macroblocks flagged as errors keep the stream's last good pixels ----
+
+int mi_dv_mb_rects(int system, int seq, int slot, int m, int rect[3][4]) {
+  const Row* r = find(system);
+  if (!rect || !r || seq < 0 || seq >= r->place_seqs || slot < 0 || slot >= 27 || m < 0 || m >= 5)
+    return fail(nullptr, MI_DV_ERR_ARG, "mi_dv_mb_rects: system %d, sequence %d, segment %d, macroblock %d out of range", system, seq, slot, m);
+  Rect q[3];
+  r->rects((uint32_t)seq, (uint32_t)slot, (uint32_t)m, q);
+  for (int pl = 0; pl < 3; pl++) {
+    rect[pl][0] = (int)q[pl].x;
+    rect[pl][1] = (int)q[pl].y;
+    rect[pl][2] = (int)q[pl].w;
+    rect[pl][3] = (int)q[pl].h;
+  }
+  return MI_DV_OK;
+}
+
+int mi_dv_held_macroblocks(int system, const uint8_t* frame, size_t len, unsigned sta_mask) {
+  const Row* r = find(system);
+  if (!r) return fail(nullptr, MI_DV_ERR_ARG, "mi_dv_held_macroblocks: unknown system %d", system);
+  if (sta_mask > 0xFFFFu) return fail(nullptr, MI_DV_ERR_ARG, "mi_dv_held_macroblocks: STA mask 0x%x: at most 0xFFFF", sta_mask);
+  if (!frame || len < (size_t)r->frame_bytes)
+    return fail(nullptr, MI_DV_ERR_ARG, "mi_dv_held_macroblocks: %s frames have %d bytes", r->frames, r->frame_bytes);
+  if (!sta_mask) sta_mask = MI_DV_STA_ERRORS;
+  int held = 0;
+  for (int seq = 0; seq < r->place_seqs; seq++)
+    for (int v = 0; v < 135; v++) held += (int)(sta_mask >> (frame[(size_t)(seq * 150 + 7 + v + v / 15) * 80 + 3] >> 4) & 1u);
+  return held;
+}
+
+int mi_dv_decode_batch_held(mi_dv_ctx* c, int system, const void* d_frames, int n, void* d_pics, int n_runs, const int* run_len,
+                            const void* d_prev, unsigned sta_mask) {
+  const Row* r = find(system);
+  if (!r) return fail(c, MI_DV_ERR_ARG, "mi_dv_decode_batch_held: unknown system %d", system);
+  return decode_held(c, *r, "mi_dv_decode_batch_held", d_frames, n, d_pics, n_runs, run_len, d_prev, sta_mask);
+}
+
+int mi_dv_hold_stats(mi_dv_ctx* c, long long* held) {
+  if (!c || !held) return MI_DV_ERR_ARG;
+  DVCHK(c, hipSetDevice(c->device));
+  DVCHK(c, hipStreamSynchronize(c->stream));
+  unsigned long long v = 0;
+  if (c->hold.counted) {  // the partial counts (dv_hold_kernels.h: kHoldCounters)
+    std::vector<unsigned long long> part((size_t)kHoldCounters * kHoldCounterStride);
+    DVCHK(c, hipMemcpyAsync(part.data(), c->hold.d_held, part.size() * sizeof part[0], hipMemcpyDeviceToHost, c->stream));
+    DVCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < kHoldCounters; i++) v += part[(size_t)i * kHoldCounterStride];
+  }
+  *held = (long long)v;
+  return MI_DV_OK;
+}
+
+int mi_dv_hold_times(mi_dv_ctx* c, float* total_ms, int* launches) {
+  if (!c || !total_ms || !launches) return MI_DV_ERR_ARG;
+  DVCHK(c, hipSetDevice(c->device));
+  DVCHK(c, hipStreamSynchronize(c->stream));
+  float sum = 0.f;
+  for (auto& e : c->hold.ev_used) {
+    float ms = 0.f;
+    DVCHK(c, hipEventElapsedTime(&ms, e.first, e.second));
+    sum += ms;
+  }
+  *total_ms = sum;
+  *launches = 3 * (int)c->hold.ev_used.size();  // k_dv_hold_mask, k_dv_hold_carry, k_dv_hold_copy
+  for (auto& e : c->hold.ev_used) c->ev_free.push_back(e);
+  c->hold.ev_used.clear();
+  return MI_DV_OK;
+}
+
+int mi_dv_hold_reset(mi_dv_ctx* c) {
+  if (!c) return MI_DV_ERR_ARG;
+  hold_forget(c);
+  return MI_DV_OK;
+}
+
+int mi_dv_decode_frame_held(mi_dv_ctx* c, int system, const uint8_t* frame, size_t len, uint8_t* const planes[3],
+                            const int strides[3], unsigned sta_mask, int* held) {
+  const char* who = "mi_dv_decode_frame_held";
+  // a refused frame, and one that failed on the way, leave no picture behind: the next frame has no source
+  const Row* r = find(system);
+  int rc = !r ? fail(c, MI_DV_ERR_ARG, "%s: unknown system %d", who, system)
+           : sta_mask > 0xFFFFu ? fail(c, MI_DV_ERR_ARG, "%s: STA mask 0x%x: one bit per STA value, at most 0xFFFF", who, sta_mask)
+                                : check_one(c, *r, who, frame, len, planes, strides);
+  if (rc != MI_DV_OK) {
+    hold_forget(c);
+    return rc;
+  }
+  mi_dv_ctx::Hold& h = c->hold;
+  const int id = r->id;
+  const bool had = h.kept == id;
+  hold_forget(c);  // (until this frame's picture is there; a picture of another system is no source for a later frame)
+  DVCHK(c, hipSetDevice(c->device));
+  rc = one_frame_buffers(c, (size_t)r->frame_bytes, (size_t)r->pic_bytes);
+  if (rc != MI_DV_OK) return rc;
+  for (uint8_t*& d : h.keep[id])
+    if (!d) DVCHK(c, hipMalloc((void**)&d, (size_t)r->pic_bytes));
+  uint8_t* const last = h.keep[id][h.cur[id]];
+  uint8_t* const now = h.keep[id][h.cur[id] ^ 1];
+  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, (size_t)r->frame_bytes, hipMemcpyHostToDevice, c->stream));
+  rc = decode_held(c, *r, who, c->d_frame, 1, now, 0, nullptr, had ? last : nullptr, sta_mask);
+  if (rc != MI_DV_OK) return rc;
+  rc = planes_out(c, *r, now, planes, strides);
+  if (rc != MI_DV_OK) return rc;
+  if (held) {
+    long long v = 0;
+    rc = mi_dv_hold_stats(c, &v);
+    if (rc != MI_DV_OK) return rc;
+    *held = (int)v;
+  }
+  h.cur[id] ^= 1;
+  h.kept = id;
   return MI_DV_OK;
 }
 

@@ -24,6 +24,13 @@
  * Shape: lib/video_rtjpeg.c's own — synchronous, one packet in, one picture out, into the caller's frame with the
  * caller's strides (copy mode; a skipped frame, f == NULL, consumes its packet and decodes nothing).
  *
+ * Damage.  A DV stream flags the macroblocks a deck could not correct (STA, the high nibble of byte 3 of a DIF block), and
+ * libavcodec keeps the last good pixels there.  With MI_DV_HOLD=1 in the process environment .decode does the same: it
+ * calls mi_dv_decode_frame_held with the default mask (MI_DV_STA_ERRORS), the instance keeps the last DECODED picture as
+ * the source (a skipped frame decodes nothing and leaves it alone), and .resync forgets it (mi_dv_hold_reset).  Opt-in
+ * because which STA values mean "error" is this repository's reading of IEC 61834-2 from memory, unpinned like the decoder
+ * itself; unset, or set to anything else, the wrapper calls mi_dv_decode_frame_sys exactly as before.
+ *
  * PARITY UNPINNED: see include/mi_dv.h.
  */
 #include <stdlib.h>
@@ -57,6 +64,13 @@ static const uint32_t dv_fourccs[] = {
  * that .probe and .init of one process agree) */
 static int dv_625_411_opted_in(void) {
   const char *e = getenv("MI_DV_625_411");
+  return e && !strcmp(e, "1");
+}
+
+/* MI_DV_HOLD=1 in the process environment: macroblocks flagged as errors keep the last decoded picture's pixels (read where
+ * it is needed, like MI_DV_625_411) */
+static int dv_hold_opted_in(void) {
+  const char *e = getenv("MI_DV_HOLD");
   return e && !strcmp(e, "1");
 }
 
@@ -125,8 +139,10 @@ static gavl_source_status_t decode_dv_hip(bgav_stream_t *s, gavl_video_frame_t *
     bgav_stream_done_packet_read(s, p);
     return GAVL_SOURCE_OK;
   }
-  if (mi_dv_decode_frame_sys(priv->ctx, priv->system, p->buf.buf, (size_t)p->buf.len, (uint8_t *const *)f->planes,
-                             f->strides) != MI_DV_OK) {
+  if ((dv_hold_opted_in() ? mi_dv_decode_frame_held(priv->ctx, priv->system, p->buf.buf, (size_t)p->buf.len,
+                                                    (uint8_t *const *)f->planes, f->strides, MI_DV_STA_ERRORS, NULL)
+                          : mi_dv_decode_frame_sys(priv->ctx, priv->system, p->buf.buf, (size_t)p->buf.len,
+                                                   (uint8_t *const *)f->planes, f->strides)) != MI_DV_OK) {
     gavl_log(GAVL_LOG_ERROR, LOG_DOMAIN, "Decoding failed: %s", mi_dv_last_error(priv->ctx));
     bgav_stream_done_packet_read(s, p);
     return GAVL_SOURCE_EOF; /* never abort: errors are EOF + a log line, as everywhere in the library */
@@ -134,6 +150,12 @@ static gavl_source_status_t decode_dv_hip(bgav_stream_t *s, gavl_video_frame_t *
   bgav_set_video_frame_from_packet(p, f);
   bgav_stream_done_packet_read(s, p);
   return GAVL_SOURCE_OK;
+}
+
+/* .resync (after a seek): the picture decoded last is not the stream's previous one any more */
+static void resync_dv_hip(bgav_stream_t *s) {
+  dv_hip_priv_t *priv = s->decoder_priv;
+  if (priv && dv_hold_opted_in()) mi_dv_hold_reset(priv->ctx);
 }
 
 static void close_dv_hip(bgav_stream_t *s) {
@@ -151,6 +173,7 @@ static bgav_video_decoder_t dv_hip_decoder = {
     .init = init_dv_hip,
     .decode = decode_dv_hip,
     .close = close_dv_hip,
+    .resync = resync_dv_hip,
 };
 
 void bgav_init_video_decoders_dv_mi355x(void) { bgav_video_decoder_register(&dv_hip_decoder); }

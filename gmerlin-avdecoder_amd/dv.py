@@ -24,7 +24,9 @@ GEOMETRY = {SYS_525_60: (FRAME_BYTES, PICTURE_BYTES, ((W, H), (CW, H), (CW, H)))
 EXPORTS = ["mi_dv_device_count", "mi_dv_create", "mi_dv_destroy", "mi_dv_last_error", "mi_dv_dev_alloc", "mi_dv_dev_free",
            "mi_dv_h2d", "mi_dv_d2h", "mi_dv_sync", "mi_dv_decode_batch", "mi_dv_kernel_times", "mi_dv_decode_frame",
            "mi_dv_copy_tables", "mi_dv_system_of", "mi_dv_decode_batch_sys", "mi_dv_decode_frame_sys", "mi_dv_mb_place",
-           "mi_dv_profile_of", "mi_dv_kind_of"]
+           "mi_dv_profile_of", "mi_dv_kind_of", "mi_dv_mb_rects", "mi_dv_held_macroblocks", "mi_dv_decode_batch_held",
+           "mi_dv_hold_stats", "mi_dv_hold_times", "mi_dv_decode_frame_held", "mi_dv_hold_reset"]
+STA_ERRORS = 0x8080  # the default mask of held macroblocks: STA 0111 and 1111 (include/mi_dv.h: MI_DV_STA_ERRORS)
 _LIB = None
 u8p = C.POINTER(C.c_uint8)
 
@@ -71,6 +73,14 @@ def load():
     L.mi_dv_decode_batch_sys.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.mi_dv_decode_frame_sys.argtypes = [vp, C.c_int, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int)]
     L.mi_dv_mb_place.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2
+    L.mi_dv_mb_rects.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int * 4)]
+    L.mi_dv_held_macroblocks.argtypes = [C.c_int, u8p, C.c_size_t, C.c_uint]
+    L.mi_dv_decode_batch_held.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int), vp, C.c_uint]
+    L.mi_dv_hold_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.mi_dv_hold_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    L.mi_dv_decode_frame_held.argtypes = [vp, C.c_int, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int), C.c_uint,
+                                          C.POINTER(C.c_int)]
+    L.mi_dv_hold_reset.argtypes = [vp]
     _LIB = L
     return L
 
@@ -129,6 +139,27 @@ def mb_place(system, seq, slot, m):
     if system == SYS_625_50_411:
         raise MiDvError(f"mb_place: system {system} is place_of's (as kind_of is to profile_of)")
     return place_of(system, seq, slot, m)
+
+
+def mb_rects(system, seq, slot, m):
+    """the three rectangles (x, y, w, h) macroblock m of segment `slot` of sequence `seq` covers, of Y, Cb and Cr, each in
+    its plane's own pixels; `seq` as place_of takes it (host-side)"""
+    r = (C.c_int * 4 * 3)()
+    L = load()
+    if L.mi_dv_mb_rects(system, seq, slot, m, r) != 0:
+        raise MiDvError(L.mi_dv_last_error(None).decode())
+    return tuple(tuple(q) for q in r)
+
+
+def held_macroblocks(frame, system, sta_mask=0):
+    """how many macroblocks of a frame the mask holds: those whose STA nibble is a set bit of it (0: STA_ERRORS)
+    (host-side)"""
+    frame = np.ascontiguousarray(frame, np.uint8)
+    L = load()
+    n = L.mi_dv_held_macroblocks(system, frame.ctypes.data_as(u8p), frame.nbytes, sta_mask)
+    if n < 0:
+        raise MiDvError(L.mi_dv_last_error(None).decode())
+    return n
 
 
 class MiDv:
@@ -208,6 +239,66 @@ class MiDv:
         else:
             self._chk(self.L.mi_dv_decode_frame_sys(self.c, system, frame.ctypes.data_as(u8p), frame.nbytes, pp, st))
         return planes
+
+    # ---- macroblocks flagged as errors keep the stream's last good pixels (include/mi_dv.h) ----
+    def decode_batch_held(self, system, d_frames, n, d_pics, runs=None, d_prev=None, sta_mask=0):
+        """decode_batch_sys, then held macroblocks from the nearest earlier picture of their run in which they are good,
+        else from the run's picture of d_prev (len(runs) pictures back to back on the device), else left as decoded.
+        runs: the lengths of the runs of consecutive frames of one stream (None: one run)"""
+        rl = (C.c_int * len(runs))(*runs) if runs else None
+        self._chk(self.L.mi_dv_decode_batch_held(self.c, system, d_frames, n, d_pics, len(runs) if runs else 0, rl, d_prev, sta_mask))
+
+    def decode_frames_held(self, frames, system, runs=None, prev=None, sta_mask=0):
+        """host frames -> host pictures through decode_batch_held; prev: one host picture per run, or None"""
+        fb, pb, _ = geometry(system)
+        frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, fb)
+        n = frames.shape[0]
+        if prev is not None:
+            prev = np.ascontiguousarray(prev, np.uint8).reshape(len(runs) if runs else 1, pb)
+        df, dp = self.alloc(n * fb), self.alloc(n * pb)
+        dq = self.alloc(prev.nbytes) if prev is not None else None
+        try:
+            self.h2d(df, frames)
+            if prev is not None:
+                self.h2d(dq, prev)
+            self.decode_batch_held(system, df, n, dp, runs, dq, sta_mask)
+            self.sync()
+            return self.d2h(dp, n * pb).reshape(n, pb)
+        finally:
+            self.free(df)
+            self.free(dp)
+            if dq:
+                self.free(dq)
+
+    def decode_frame_held(self, frame, system, strides=None, sta_mask=0):
+        """decode_frame with held macroblocks from the picture of the frame this call decoded last (none: the first frame,
+        after hold_reset, after a frame of another system or a refused one) -> (planes, macroblocks taken from it)"""
+        _, _, planes_wh = geometry(system)
+        if strides is None:
+            strides = tuple(w for w, _ in planes_wh)
+        frame = np.ascontiguousarray(frame, np.uint8)
+        planes = [np.zeros(strides[i] * planes_wh[i][1], np.uint8) for i in range(3)]
+        pp = (u8p * 3)(*[p.ctypes.data_as(u8p) for p in planes])
+        st = (C.c_int * 3)(*strides)
+        held = C.c_int()
+        self._chk(self.L.mi_dv_decode_frame_held(self.c, system, frame.ctypes.data_as(u8p), frame.nbytes, pp, st, sta_mask,
+                                                 C.byref(held)))
+        return planes, held.value
+
+    def hold_reset(self):
+        self._chk(self.L.mi_dv_hold_reset(self.c))
+
+    def hold_stats(self):
+        """the macroblocks the last held batch took from another picture"""
+        v = C.c_longlong()
+        self._chk(self.L.mi_dv_hold_stats(self.c, C.byref(v)))
+        return v.value
+
+    def hold_times(self):
+        """(total milliseconds, launches) of the hold pass since the last call; kernel_times keeps k_dv_decode's"""
+        ms, n = C.c_float(), C.c_int()
+        self._chk(self.L.mi_dv_hold_times(self.c, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def close(self):
         if self.c:

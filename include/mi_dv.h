@@ -71,7 +71,8 @@ int mi_dv_sync(mi_dv_ctx *c);
 /* The hot path: n DIF frames resident in device memory (back to back, MI_DV_FRAME_BYTES each, d_frames 4-byte aligned)
  * -> n pictures (back to back, MI_DV_PICTURE_BYTES each: Y 720 x 480, Cb 180 x 480, Cr 180 x 480, tightly packed;
  * d_pics 8-byte aligned).  Queued on the instance's stream; pair with mi_dv_sync.  Any 120,000 bytes decode to
- * something (damaged frames are not detected, as in the oracle). */
+ * something (damaged frames are not detected, as in the oracle; mi_dv_decode_batch_held and mi_dv_decode_frame_held
+ * below read what a stream says about its own damage). */
 int mi_dv_decode_batch(mi_dv_ctx *c, const void *d_frames, int n, void *d_pics);
 /* Device time of k_dv_decode: every mi_dv_decode_batch brackets its launch with HIP events on the instance's stream;
  * this sums them over the launches since the last call (synchronises, then forgets them). */
@@ -124,6 +125,55 @@ int mi_dv_decode_frame_sys(mi_dv_ctx *c, int system, const uint8_t *frame, size_
  * byte order, 0..19 / 0..23 (channel seq / 10, seq / 12); x in 16-pixel columns (0..44), y in 8-line rows (0..59 /
  * 0..71).  Host only; MI_DV_ERR_ARG for arguments out of range. */
 int mi_dv_mb_place(int system, int seq, int slot, int m, int *x, int *y);
+
+/* ---- macroblocks the stream flags as errors keep the stream's last good pixels ----
+ *
+ * Byte 3 of every compressed macroblock (DIF block) is STA | QNO.  The calls above drop STA, so to them "damaged frames
+ * are not detected"; the calls below read it.  A macroblock is HELD when bit STA (the high nibble, 0..15) is set in a
+ * 16-bit mask.  The default, MI_DV_STA_ERRORS, holds STA 0111 and 1111 ("error exists"); 0010, 0100, 0110, 1010, 1100
+ * and 1110 say that the SOURCE already concealed the macroblock: its data are valid and are decoded.  UNPINNED like the
+ * rest of this decoder: this is the repository's reading of IEC 61834-2 from memory.  The rule is this one mask, so
+ * correcting it is one line, and every call takes the caller's own (0: the default).
+ * A held macroblock is held as a whole.  Its neighbours in the video segment, which may have lent it bits in the third
+ * pass, are decoded as they are.
+ * A held macroblock of picture k of a stream is that macroblock of the nearest earlier picture of the stream in which it
+ * is good; where there is none it stays what the decoder made of its bytes. */
+enum { MI_DV_STA_ERRORS = 0x8080 };
+/* The three rectangles {x, y, w, h} macroblock m (0..4) of video segment `slot` (0..26) of DIF sequence `seq` (as
+ * mi_dv_mb_place takes it) covers: rect[0] of Y, rect[1] of Cb, rect[2] of Cr, each in its plane's own pixels.  4:1:1:
+ * 32 x 8 and 8 x 8, in column 22 16 x 16 and 4 x 16 (the chroma block's halves one above the other); 625/50 4:2:0:
+ * 16 x 16 and 8 x 8; 4:2:2: 16 x 8 and 8 x 8.  Macroblock 5 (27 seq + slot) + m of a frame; its DIF block is block
+ * 7 + v + v / 15 of its sequence, v = 5 slot + m.  Host only; MI_DV_ERR_ARG for arguments out of range. */
+int mi_dv_mb_rects(int system, int seq, int slot, int m, int rect[3][4]);
+/* How many macroblocks of a frame (at least the system's frame bytes) the mask holds (0: MI_DV_STA_ERRORS).  Host only;
+ * MI_DV_ERR_ARG for an unknown system, a NULL or short frame, a mask above 0xFFFF. */
+int mi_dv_held_macroblocks(int system, const uint8_t *frame, size_t len, unsigned sta_mask);
+/* mi_dv_decode_batch_sys with held macroblocks.  The n frames are n_runs runs of consecutive frames of one stream each
+ * (run_len adds up to n; n_runs 0 or run_len NULL: one run).  d_prev: the picture before each run, n_runs pictures back
+ * to back (8-byte aligned, not overlapping d_pics), or NULL; where a macroblock is good in no earlier picture of its run
+ * it comes from the run's picture of d_prev.  sta_mask 0: MI_DV_STA_ERRORS.  Queued on the instance's stream like
+ * mi_dv_decode_batch_sys; buffers of the instance grow when needed (the call may synchronise then) and never shrink.
+ * With no macroblock held the pictures are those of mi_dv_decode_batch_sys byte for byte; a run of one picture without
+ * d_prev has no source and costs nothing more.  MI_DV_ERR_ARG, with nothing launched, for an unknown system, n out of
+ * range or misaligned buffers (the rules of mi_dv_decode_batch), a run length <= 0, lengths that do not add up to n,
+ * d_prev overlapping d_pics, a mask above 0xFFFF. */
+int mi_dv_decode_batch_held(mi_dv_ctx *c, int system, const void *d_frames, int n, void *d_pics, int n_runs, const int *run_len,
+                            const void *d_prev, unsigned sta_mask);
+/* The macroblocks the last held batch took from another picture (held ones without a source do not count).  Synchronises. */
+int mi_dv_hold_stats(mi_dv_ctx *c, long long *held);
+/* Device time of the hold pass alone (k_dv_hold_mask, k_dv_hold_carry, k_dv_hold_copy: three launches a batch that has a
+ * source) since the last call, as mi_dv_kernel_times, which keeps counting k_dv_decode alone. */
+int mi_dv_hold_times(mi_dv_ctx *c, float *total_ms, int *launches);
+/* mi_dv_decode_frame_sys with held macroblocks: the instance keeps the picture of the last frame this call decoded on
+ * the device, and that picture is the next frame's source, as d_prev is a run's: the whole picture, so a macroblock
+ * held in two frames running keeps what the kept picture holds.  The checks and messages of mi_dv_decode_frame_sys.  No
+ * source, so that held macroblocks stay as decoded: for the first frame, the first after mi_dv_hold_reset, the first of
+ * another system than the frame before, and a frame that follows a refused one.  *held (may be NULL): the macroblocks
+ * taken from the kept picture. */
+int mi_dv_decode_frame_held(mi_dv_ctx *c, int system, const uint8_t *frame, size_t len, uint8_t *const planes[3],
+                            const int strides[3], unsigned sta_mask, int *held);
+/* Forget the kept picture (a decoder's .resync: after a seek the frame before is not the stream's previous picture). */
+int mi_dv_hold_reset(mi_dv_ctx *c);
 
 #ifdef __cplusplus
 }
