@@ -13,6 +13,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import rtjlib as R  # noqa: E402
+from edge_packets import adversarial_packet  # noqa: E402,F401 (the builder lives with the other edge packets)
 
 
 def ref_lb8_cb8(ref):
@@ -20,31 +21,6 @@ def ref_lb8_cb8(ref):
     off = 128 + 1024 + 4 * 256
     ints = (C.c_int * 2).from_address(ref.h + off)
     return int(ints[0]), int(ints[1])
-
-
-def adversarial_packet(rng, w, h, Q, lb8, cb8, skip_prob=0.0):
-    nblk = (w // 16) * (h // 16) * 6
-    body = bytearray()
-    for b in range(nblk):
-        if rng.random() < skip_prob:
-            body.append(255)
-            continue
-        bt8 = lb8 if (b % 6) < 4 else cb8
-        blk = [int(rng.integers(0, 255))] + [int(x) for x in rng.integers(0, 256, bt8)]
-        co = bt8 + 1
-        while co < 64:
-            if rng.random() < 0.3:
-                run = int(rng.integers(1, 64 - co + 1))
-                blk.append(63 + run)
-                co += run
-            else:
-                blk.append(int(rng.integers(-64, 64)) & 0xFF)
-                co += 1
-        body += bytes(blk)
-    total = 12 + len(body)
-    hdr = bytes([total & 255, (total >> 8) & 255, (total >> 16) & 255, (total >> 24) & 255, 12, 0,
-                 w & 255, w >> 8, h & 255, h >> 8, Q, 0])
-    return np.frombuffer(hdr + bytes(body), dtype=np.uint8).copy()
 
 
 def main():

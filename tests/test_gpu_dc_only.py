@@ -1,13 +1,16 @@
 """Pictures built around DC-only blocks ("DC, zeros, one run": the pixel clamp((int16(DC * q0) + 4) >> 3) 64 times
 over, lib/RTjpeg.c:2223-2238), which is what five of six chroma blocks of the bench content are: flat chroma under busy
 luma, half-flat pictures (macroblock groups that mix DC-only and busy blocks), all-flat pictures, unchanged (0xFF)
-blocks among them, and DC-only blocks spelled in ways the encoder never uses.  Every case runs through both launch
-shapes of k_decode (a wave per part of a group / a wave that takes all three parts, MI_RTJ_ROTATE=1).  Bit-exact
-against the oracle everywhere.  (Round 2 had a second kernel for the busy blocks of mostly-flat groups; it was slower
-and is gone — the cases stay.)"""
+blocks among them, and DC-only blocks spelled in ways the encoder never uses.  Every case runs through the three forms
+of a batch launch, each forced by the environment and checked against what the plan says ran: a wave per part of a
+group (k_decode<false, false>, MI_RTJ_ROTATE=0), the split form (k_decode_split: luma waves, chroma waves that pool the
+busy blocks of three groups, and k_decode_list for what they decline; MI_RTJ_ROTATE=1 MI_RTJ_SPLIT=1) and the classic
+form (k_decode<true, false>: a wave takes all three parts of its groups; MI_RTJ_ROTATE=1 MI_RTJ_SPLIT=0).  Bit-exact
+against the oracle everywhere."""
 import numpy as np
 import pytest
 
+import edge_packets as E
 import rtjlib as R
 import test_gpu_parity as T
 from pkg import P
@@ -15,10 +18,23 @@ from pkg import P
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(params=["part-per-wave", "three-parts-per-wave"])
+# form -> (environment of the plan, what plan.decode_form() says ran)
+FORMS = {
+    "part-per-wave": (dict(MI_RTJ_ROTATE="0"), -1),
+    "split": (dict(MI_RTJ_ROTATE="1", MI_RTJ_SPLIT="1"), 0),
+    "classic": (dict(MI_RTJ_ROTATE="1", MI_RTJ_SPLIT="0"), 1),
+}
+
+
+@pytest.fixture(params=list(FORMS))
 def dev(request, monkeypatch):
-    monkeypatch.setenv("MI_RTJ_ROTATE", "1" if request.param == "three-parts-per-wave" else "0")
+    env, form = FORMS[request.param]
+    for k in ("MI_RTJ_ROTATE", "MI_RTJ_SPLIT", "MI_RTJ_DEC_SLOTS"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
     d = P.MiRtj()
+    d.expect_form = form
     yield d
     d.close()
 
@@ -34,6 +50,7 @@ def decode_batch(dev, pkts, prefill=0):
     plan.decode(d_stream, d_out)
     plan.decode(d_stream, d_out)
     dev.sync()
+    assert plan.decode_form()[0] == dev.expect_form, (plan.decode_form(), dev.expect_form)
     outs = [dev.d2h(d_out, sizes[i], offset=int(oo[i])) for i in range(len(pkts))]
     plan.close()
     dev.free(d_stream)
@@ -96,35 +113,5 @@ def test_unchanged_blocks_among_dc_only_ones(dev):
 def test_dc_only_blocks_spelled_unusually(dev):
     """DC followed by zero coefficients written out, by several short runs, by a run that overshoots, or with a
     non-zero raw byte: none is the encoder's "DC, zeros, one run" form; mixed with blocks that are."""
-    rng = np.random.default_rng(12)
-    w, h = 512, 64
-    nblk = (w // 16) * (h // 16) * 6
-    pkts = []
-    for Q in (255, 192, 128, 60):
-        _, _, lb8, cb8, _, _ = R.oracle_tables(Q)
-        body = bytearray()
-        for b in range(nblk):
-            bt8 = lb8 if (b % 6) < 4 else cb8
-            left = 63 - bt8
-            kind = int(rng.integers(0, 7))
-            dc = int(rng.integers(0, 255))
-            if kind <= 2:    # the encoder's form
-                blk = [dc] + [0] * bt8 + [63 + left]
-            elif kind == 3:  # zeros spelled out, then a shorter run
-                k = int(rng.integers(1, min(left, 6)))
-                blk = [dc] + [0] * bt8 + [0] * k + ([63 + left - k] if left - k else [])
-            elif kind == 4:  # two runs
-                k = int(rng.integers(1, left)) if left > 1 else 1
-                blk = [dc] + [0] * bt8 + [63 + k] + ([63 + left - k] if left - k else [])
-            elif kind == 5:  # a run that overshoots the block
-                blk = [dc] + [0] * bt8 + [127]
-            else:            # one non-zero coefficient
-                blk = [dc] + [0] * bt8 + [3, 63 + left - 1] if left > 1 else [dc] + [0] * bt8 + [3]
-                if bt8:
-                    blk[1 + int(rng.integers(0, bt8))] = int(rng.integers(1, 256)) if rng.random() < 0.5 else 0
-            body += bytes(x & 0xFF for x in blk)
-        total = 12 + len(body)
-        hdr = bytes([total & 255, (total >> 8) & 255, (total >> 16) & 255, (total >> 24) & 255, 12, 0,
-                     w & 255, w >> 8, h & 255, h >> 8, Q, 0])
-        pkts.append(np.frombuffer(hdr + bytes(body), dtype=np.uint8).copy())
+    pkts = E.dc_spelling_packets(seed=12, w=512, h=64)
     check(pkts, decode_batch(dev, pkts, prefill=9), prefill=9)

@@ -81,14 +81,14 @@ def compare(outs, wants, pkts, cls, form, prefill, kinds=None, max_groups=None, 
                              f"got {int(got[off])} want {int(want[off])}; {where}")
 
 
-def run_form(dev, monkeypatch, pkts, wants, cls, form, env, expect_form, prefill, kinds=None, max_groups=None):
+def run_form(dev, monkeypatch, pkts, wants, cls, form, env, expect_form, prefill, kinds=None, max_groups=None, launches=1):
     with monkeypatch.context() as m:
         for k in ("MI_RTJ_ROTATE", "MI_RTJ_SPLIT", "MI_RTJ_DEC_SLOTS"):
             m.delenv(k, raising=False)
         for k, v in env.items():
             m.setenv(k, v)
         rep = {}
-        outs = T.batch_decode(dev, pkts, prefill=prefill, align=1, guard=GUARD, odd16=True, report=rep)
+        outs = T.batch_decode(dev, pkts, prefill=prefill, align=1, guard=GUARD, odd16=True, report=rep, launches=launches)
     assert rep["form"] == expect_form, f"class {cls}, form {form}: the plan ran form {rep['form']}, not {expect_form}"
     assert any(int(o) % 256 for o in rep["out_offsets"]) and all(int(o) % 16 == 0 for o in rep["out_offsets"])
     compare(outs, wants, pkts, cls, form, prefill, kinds, max_groups, slots=int(env.get("MI_RTJ_DEC_SLOTS", 0)) or None)

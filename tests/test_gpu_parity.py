@@ -6,6 +6,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import edge_packets as E
 import launch_shapes as LS
 import rtjlib as R
 from pkg import P
@@ -213,14 +214,7 @@ def test_skip_blocks_leave_destination_untouched_in_batches(dev):
 def test_random_token_streams(dev):
     """Adversarial blocks (random bytes, random runs, some 0xFF) at qualities where the int16
     narrowing of RTjpeg_s2b and DESCALE is observable."""
-    from golden.make_golden import adversarial_packet
-    rng = np.random.default_rng(2025)
-    pkts, qs = [], []
-    for Q in (1, 2, 3, 8, 31, 129, 192, 255):
-        _, _, lb8, cb8, _, _ = R.oracle_tables(Q)
-        for (w, h) in ((48, 32), (160, 16)):
-            pkts.append(adversarial_packet(rng, w, h, Q, lb8, cb8, skip_prob=0.1))
-            qs.append(Q)
+    pkts, qs = E.adversarial_packets(seed=2025)
     # each packet gets its own decoder state in the oracle; do the same on the device
     for p, Q in zip(pkts, qs):
         w, h = int(p[6]) | (int(p[7]) << 8), int(p[8]) | (int(p[9]) << 8)
@@ -333,35 +327,8 @@ def test_serial_and_parallel_index_agree(dev, monkeypatch):
 def test_chunk_boundaries_and_long_blocks(dev):
     """Streams built to stress the chunked index: maximal 64-byte blocks (no zero runs), minimal
     1-byte (0xFF) blocks, and mixtures, so macroblocks straddle every chunk boundary differently."""
-    rng = np.random.default_rng(77)
     w, h = 1024, 256  # 1024 macroblocks: long-block packets span ~110 chunks
-    nblk = (w // 16) * (h // 16) * 6
-    pkts = []
-    for Q, mode in [(255, "long"), (255, "skip"), (255, "mix"), (100, "long"), (100, "mix"), (255, "runs")]:
-        _, _, lb8, cb8, _, _ = R.oracle_tables(Q)
-        body = bytearray()
-        for b in range(nblk):
-            bt8 = lb8 if (b % 6) < 4 else cb8
-            kind = mode if mode != "mix" else ["long", "skip", "short", "runs"][int(rng.integers(0, 4))]
-            if kind == "skip":
-                body.append(255)
-                continue
-            blk = [int(rng.integers(0, 255))] + [int(x) for x in rng.integers(0, 256, bt8)]
-            left = 63 - bt8
-            if kind == "long":      # every remaining coefficient spelled out
-                blk += [int(x) & 0xFF for x in rng.integers(-64, 64, left)]
-            elif kind == "short":   # one run to the end
-                blk.append(63 + left)
-            else:                   # unit runs: many weight-1 run tokens (byte 64)
-                while left > 0:
-                    r = int(rng.integers(1, min(left, 3) + 1))
-                    blk.append(63 + r)
-                    left -= r
-            body += bytes(blk)
-        total = 12 + len(body)
-        hdr = bytes([total & 255, (total >> 8) & 255, (total >> 16) & 255, (total >> 24) & 255, 12, 0,
-                     w & 255, w >> 8, h & 255, h >> 8, Q, 0])
-        pkts.append(np.frombuffer(hdr + bytes(body), dtype=np.uint8).copy())
+    pkts = E.chunk_boundary_packets(seed=77, w=w, h=h)
     outs = batch_decode(dev, pkts, prefill=3)
     for p, got in zip(pkts, outs):
         want = np.full(frame_bytes(w, h), 3, np.uint8)
@@ -410,65 +377,12 @@ def test_fuzz_arbitrary_bytes(dev):
         assert first_diff(got, want) is None, (i, first_diff(got, want))
 
 
-def _packet_from_blocks(w, h, Q, blocks):
-    body = b"".join(bytes(b) for b in blocks)
-    total = 12 + len(body)
-    hdr = bytes([total & 255, (total >> 8) & 255, (total >> 16) & 255, (total >> 24) & 255, 12, 0,
-                 w & 255, w >> 8, h & 255, h >> 8, Q, 0])
-    return np.frombuffer(hdr + body, dtype=np.uint8).copy()
-
-
 def test_low_4x4_transform_path_and_its_boundary(dev):
     """k_decode runs a four-input transform when no block of a wave has a coefficient outside the low
     4x4, and a three-input one when none reaches row 3 or column 3 either.  Packets are built so that whole waves qualify, whole waves do not, a wave stops qualifying from
     one macroblock group to the next, and the single coefficient sits on every one of the 63 AC slots
     (inside, on the edge of and outside the 4x4) with values where the int16 narrowing shows."""
-    rng = np.random.default_rng(99)
-    pkts = []
-    for Q in (255, 200, 150, 3):
-        _, _, lb8, cb8, _, _ = R.oracle_tables(Q)
-        for (w, h, mode) in ((512, 64, "one"), (1024, 32, "flat_then_busy"), (512, 32, "dc_only"),
-                             (1024, 48, "three_then_four")):
-            nmb = (w // 16) * (h // 16)
-            blocks = []
-            for mb in range(nmb):
-                for k in range(6):
-                    bt8 = lb8 if k < 4 else cb8
-                    blk = [int(rng.integers(0, 255))] + [0] * bt8  # DC, raw bytes zero unless chosen below
-                    if mode == "one":
-                        slot = 1 + (mb * 6 + k) % 63          # the one AC coefficient: every slot in turn
-                    elif mode == "flat_then_busy":
-                        slot = int(rng.integers(1, 4)) if mb < nmb // 2 else int(rng.integers(1, 64))
-                    elif mode == "three_then_four":
-                        # zig-zag slots inside the low 3x3 (the three-input transform), then, from the second
-                        # third of the picture on, slots on row 3 or column 3 of the low 4x4 as well (the
-                        # four-input one), then one block per macroblock group anywhere (the full one)
-                        in3 = (1, 2, 3, 4, 5, 7, 8, 12)
-                        edge4 = (6, 9, 11, 13, 17, 18, 24)
-                        if mb < nmb // 3:
-                            slot = in3[int(rng.integers(0, len(in3)))]
-                        elif mb < 2 * nmb // 3:
-                            slot = edge4[int(rng.integers(0, len(edge4)))] if rng.random() < 0.1 else in3[int(rng.integers(0, len(in3)))]
-                        else:
-                            slot = int(rng.integers(1, 64)) if (mb % 32 == 5 and k == 2) else in3[int(rng.integers(0, len(in3)))]
-                    else:
-                        slot = 0
-                    val = int(rng.integers(-128, 64)) & 0xFF if slot else 0
-                    if slot and slot <= bt8:
-                        blk[slot] = val
-                        blk.append(63 + 63 - bt8)             # one run over all token slots
-                    elif slot:
-                        before = slot - bt8 - 1
-                        if before:
-                            blk.append(63 + before)
-                        blk.append(val if val < 64 or val > 127 else 1)
-                        after = 63 - slot
-                        if after:
-                            blk.append(63 + after)
-                    else:
-                        blk.append(63 + 63 - bt8)
-                    blocks.append(blk)
-            pkts.append(_packet_from_blocks(w, h, Q, blocks))
+    pkts = E.low_4x4_packets(seed=99)
     outs = batch_decode(dev, pkts, prefill=0x33)
     dec = R.OracleDecoder()
     for i, (p, got) in enumerate(zip(pkts, outs)):
@@ -642,99 +556,7 @@ def test_packed_passes_on_both_sides_of_their_16_bit_budget(dev):
     outside the budget, with sparse and dense coefficient patterns and both signs; most waves hold blocks of several
     kinds, some are all inside.  Chroma blocks get the same treatment with coefficients in the low 3x3 only (the
     three-input form has a packed twin with a budget of its own) and anywhere."""
-    import os
-    import re
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gmerlin-avdecoder_amd", "csrc",
-                            "rtj_idct_pk.h")).read()
-    slack, dc4 = (int(v) for v in re.search(r"kPkBudget = 4 \* \(32767 - (\d+) - (\d+)\)", hdr).groups())
-    classw = [int(v) for v in re.search(r"kPkClassW\[8\] = \{([^}]*)\}", hdr).group(1).split(",")]
-    rowk = [int(v) for v in re.search(r"rowk\[8\] = \{([^}]*)\}", hdr).group(1).split(",")]
-    cls = [[int(v) for v in row.split(",")] for row in re.findall(r"^\s*\{(\d, \d, \d, \d)\},", hdr, re.M)]
-    budget = 4 * (32767 - slack - dc4)
-    zz = [0, 8, 1, 2, 9, 16, 24, 17, 10, 3, 4, 11, 18, 25, 32, 40, 33, 26, 19, 12, 5, 6, 13, 20, 27, 34, 41, 48, 56, 49,
-          42, 35, 28, 21, 14, 7, 15, 22, 29, 36, 43, 50, 57, 58, 51, 44, 37, 30, 23, 31, 38, 45, 52, 59, 60, 53, 46, 39,
-          47, 54, 61, 62, 55, 63]
-    wnat = np.array([classw[cls[rowk[n >> 3]][(n & 7) >> 1]] for n in range(64)], np.int64)
-    low3 = [k for k in range(64) if (zz[k] >> 3) < 3 and (zz[k] & 7) < 3]
-    rng = np.random.default_rng(2024)
-
-    def weighted(tok, q):  # the kernel's sum for a block given its token values per zig-zag slot (slot 0: DC byte)
-        c = (((tok.astype(np.int64) * q[zz].astype(np.int64)) + 32768) % 65536) - 32768  # stored as int16
-        return int((wnat[zz] * np.abs(c)).sum())  # (q: natural order, as the kernel's table)
-
-    def block_bytes(tok, bt8):
-        out = [int(tok[0])] + [int(tok[k]) & 0xFF for k in range(1, bt8 + 1)]
-        run = 0
-        for k in range(bt8 + 1, 64):
-            if tok[k] == 0:
-                run += 1
-                continue
-            if run:
-                out.append(63 + run)
-                run = 0
-            out.append(int(tok[k]) & 0xFF)
-        if run:
-            out.append(63 + run)
-        return out
-
-    def make(q, bt8, slots, kind):
-        """kind: target position of the block's sum relative to the budget"""
-        tok = np.zeros(64, np.int64)
-        tok[0] = rng.integers(0, 255)
-        n = int(rng.integers(1, min(len(slots), 24) + 1))
-        pick = rng.choice(slots, n, replace=False)
-        tok[pick] = rng.integers(1, 64, n) * rng.choice([-1, 1], n)
-        tok[0] = max(int(tok[0]), 0)
-        target = {"in": 0.4, "edge_in": 1.0, "edge_out": 1.0, "out": 2.5}[kind] * budget
-        for _ in range(40):  # scale the AC tokens towards the target (token range -128..63; 64..127 are runs)
-            s = weighted(tok, q)
-            ac = s - int(wnat[0]) * abs(((int(tok[0]) * int(q[0]) + 32768) % 65536) - 32768)
-            if ac <= 0:
-                break
-            f = (target - (s - ac)) / ac
-            new = np.clip(np.round(tok[1:] * f), -128, 63)
-            new[(tok[1:] != 0) & (new == 0)] = 1
-            if np.array_equal(new, tok[1:]):
-                break
-            tok[1:] = new
-        if kind.startswith("edge"):
-            k = int(pick[np.argmin(wnat[[zz[p] for p in pick]] * q[[zz[p] for p in pick]])])  # the finest step available
-            step = 1 if tok[k] > 0 else -1
-            for _ in range(400):
-                s = weighted(tok, q)
-                if kind == "edge_in" and s > budget and abs(tok[k]) > 1:
-                    tok[k] -= step
-                elif kind == "edge_in" and s <= budget and -128 < tok[k] + step < 64 and weighted(np.where(np.arange(64) == k, tok + step, tok), q) <= budget:
-                    tok[k] += step
-                elif kind == "edge_out" and s <= budget and -128 < tok[k] + step < 64:
-                    tok[k] += step
-                elif kind == "edge_out" and s > budget and abs(tok[k]) > 1 and weighted(np.where(np.arange(64) == k, tok - step, tok), q) > budget:
-                    tok[k] -= step
-                else:
-                    break
-        return tok, weighted(tok, q)
-
-    pkts, seen = [], {"in": 0, "out": 0, "near": 0}
-    for Q in (255, 120):
-        liqt, ciqt, lb8, cb8, _, _ = R.oracle_tables(Q)
-        for (w, h, mix) in ((1024, 64, "mixed"), (512, 32, "all_in"), (1024, 32, "one_out_per_group")):
-            nmb = (w // 16) * (h // 16)
-            blocks = []
-            for mb in range(nmb):
-                for k in range(6):
-                    q, bt8 = (liqt, lb8) if k < 4 else (ciqt, cb8)
-                    slots = list(range(1, 64)) if (k < 4 or mb % 3) else low3[1:]
-                    if mix == "all_in":
-                        kind = ("in", "edge_in")[int(rng.integers(0, 2))]
-                    elif mix == "one_out_per_group":
-                        kind = ("edge_out" if k in (1, 4) else "out") if mb % 32 == 7 else "in"
-                    else:
-                        kind = ("in", "edge_in", "edge_out", "out")[int(rng.integers(0, 4))]
-                    tok, s = make(q, bt8, slots, kind)
-                    seen["in" if s <= budget else "out"] += 1
-                    seen["near"] += abs(s - budget) < budget // 50
-                    blocks.append(block_bytes(tok, bt8))
-            pkts.append(_packet_from_blocks(w, h, Q, blocks))
+    pkts, seen, _ = E.budget_packets(seed=2024)
     assert seen["in"] > 1000 and seen["out"] > 300 and seen["near"] > 300, seen
     outs = batch_decode(dev, pkts, prefill=0x55)
     dec = R.OracleDecoder()
