@@ -6,6 +6,7 @@
 // The checker under the test suite states the same data independently; tests/test_dv_oracle.py compares what the two
 // make of it.
 #include "dv_common.h"
+#include "dv_encode_tables.h"
 
 #include <math.h>
 #include <string.h>
@@ -93,6 +94,34 @@ bool build_tables(Tables* t) {
   for (int i = 0; i < 22; i++)
     t->shift4[i] = (uint32_t)(kQuantShift[i][0] + 1) | (uint32_t)(kQuantShift[i][1] + 1) << 4 |
                    (uint32_t)(kQuantShift[i][2] + 1) << 8 | (uint32_t)(kQuantShift[i][3] + 1) << 12;
+  return true;
+}
+
+// the encoder's side of the same code: canonical code words by (run, amplitude), the first (shortest) listing of a pair
+bool build_enc_tables(EncTables* t) {
+  memset(t, 0, sizeof *t);
+  uint32_t code = 0, prev = kLen[0];
+  for (int i = 0; i < kShort; i++) {
+    const uint32_t len = kLen[i], run = kRun[i], amp = kAmp[i];
+    code <<= (len - prev);
+    prev = len;
+    const uint32_t e = code | (len << 16);
+    if (run == 255u) {
+      t->eob = e;
+    } else {
+      if (run >= (uint32_t)kEncRuns || amp >= (uint32_t)kEncAmps) return false;
+      if (t->word[run][amp] == 0u) t->word[run][amp] = e;
+    }
+    code++;
+  }
+  if (t->eob == 0u) return false;
+  for (int a = 1; a < kEncAmps; a++)  // the unlisted pairs are spelled with these
+    if (t->word[0][a] == 0u) return false;
+  for (int r = 0; r < 6; r++)
+    if (t->word[r][0] == 0u) return false;
+  for (int i = 0; i < 22; i++)
+    t->shift4[i] = (uint32_t)kQuantShift[i][0] | (uint32_t)kQuantShift[i][1] << 4 | (uint32_t)kQuantShift[i][2] << 8 |
+                   (uint32_t)kQuantShift[i][3] << 12;
   return true;
 }
 

@@ -1,4 +1,4 @@
-// mi_dv.hip — C ABI (include/mi_dv.h) of the MI355X DV decoder (25 Mbit/s: 525/60 4:1:1, 625/50 4:2:0, 625/50 4:1:1;
+// mi_dv.hip — C ABI (include/mi_dv.h) of the MI355X DV decoder and encoder (25 Mbit/s: 525/60 4:1:1, 625/50 4:2:0, 625/50 4:1:1;
 // 50 Mbit/s: both line systems in 4:2:2).  No CPU path: without a gfx950 device every call fails with a message.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -14,6 +14,7 @@
 #include "dv_common.h"
 #include "dv_decode_kernels.h"
 #include "dv_hold_kernels.h"
+#include "dv_encode_kernels.h"
 
 using namespace midv;
 
@@ -42,6 +43,11 @@ struct mi_dv_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   Tables* d_tab = nullptr;
+  // the encoder (mi_dv_encode_*): its tables, the last batch's counts (kEncStats), one pair of events around every launch
+  // since the last mi_dv_encode_times
+  EncTables* d_enc = nullptr;
+  unsigned long long* d_enc_stats = nullptr;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> enc_ev_used;
   // one pair of events around every launch since the last mi_dv_kernel_times (recycled there)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_used, ev_free;
   // the one-frame path's buffers: as large as the largest system this instance has seen needs them
@@ -129,11 +135,20 @@ mi_dv_ctx* mi_dv_create(int device) {
     fail(nullptr, MI_DV_ERR_ARG, "internal: the variable-length code's tables are inconsistent");
     return nullptr;
   }
+  EncTables et;
+  if (!build_enc_tables(&et)) {
+    fail(nullptr, MI_DV_ERR_ARG, "internal: the variable-length code lists a pair outside the encoder's table");
+    return nullptr;
+  }
   mi_dv_ctx* c = new mi_dv_ctx();
   c->device = device;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipMalloc((void**)&c->d_tab, sizeof(Tables)) != hipSuccess ||
-      hipMemcpy(c->d_tab, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess) {
+      hipMemcpy(c->d_tab, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMalloc((void**)&c->d_enc, sizeof(EncTables)) != hipSuccess ||
+      hipMemcpy(c->d_enc, &et, sizeof et, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMalloc((void**)&c->d_enc_stats, kEncStats * sizeof(unsigned long long)) != hipSuccess ||
+      hipMemset(c->d_enc_stats, 0, kEncStats * sizeof(unsigned long long)) != hipSuccess) {
     fail(nullptr, MI_DV_ERR_HIP, "cannot set up device %d: %s", device, hipGetErrorString(hipGetLastError()));
     mi_dv_destroy(c);
     return nullptr;
@@ -146,6 +161,8 @@ void mi_dv_destroy(mi_dv_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->d_tab) (void)hipFree(c->d_tab);
+  if (c->d_enc) (void)hipFree(c->d_enc);
+  if (c->d_enc_stats) (void)hipFree(c->d_enc_stats);
   if (c->d_frame) (void)hipFree(c->d_frame);
   if (c->d_pic) (void)hipFree(c->d_pic);
   if (c->h_pic) (void)hipHostFree(c->h_pic);
@@ -156,7 +173,7 @@ void mi_dv_destroy(mi_dv_ctx* c) {
     for (uint8_t* d : k)
       if (d) (void)hipFree(d);
   if (c->hold.desc_done) (void)hipEventDestroy(c->hold.desc_done);
-  for (auto* v : {&c->ev_used, &c->ev_free, &c->hold.ev_used})
+  for (auto* v : {&c->ev_used, &c->ev_free, &c->hold.ev_used, &c->enc_ev_used})
     for (auto& e : *v) {
       (void)hipEventDestroy(e.first);
       (void)hipEventDestroy(e.second);
@@ -241,6 +258,31 @@ int launch(mi_dv_ctx* c, const char* who, const void* d_frames, int n, void* d_p
   return MI_DV_OK;
 }
 
+// the launch of a system's encoder kernel with its events; the arguments are checked by encode_batch below
+template <class Sys>
+int encode_launch(mi_dv_ctx* c, const void* d_pics, int n, void* d_frames, int flags) {
+  std::pair<hipEvent_t, hipEvent_t> ev;
+  if (!c->ev_free.empty()) {
+    ev = c->ev_free.back();
+    c->ev_free.pop_back();
+  } else {
+    DVCHK(c, hipEventCreate(&ev.first));
+    DVCHK(c, hipEventCreate(&ev.second));
+  }
+  c->enc_ev_used.push_back(ev);
+  if (c->enc_ev_used.size() > 4096) {  // nobody asks for times: keep the newest
+    c->ev_free.push_back(c->enc_ev_used.front());
+    c->enc_ev_used.erase(c->enc_ev_used.begin());
+  }
+  DVCHK(c, hipMemsetAsync(c->d_enc_stats, 0, kEncStats * sizeof(unsigned long long), c->stream));
+  DVCHK(c, hipEventRecord(ev.first, c->stream));
+  hipLaunchKernelGGL(k_dv_encode<Sys>, dim3(kEncGridX<Sys>, (unsigned)n), dim3(64), 0, c->stream, (const uint8_t*)d_pics,
+                     (uint8_t*)d_frames, (const EncTables*)c->d_enc, (uint32_t)flags, c->d_enc_stats);
+  DVCHK(c, hipGetLastError());
+  DVCHK(c, hipEventRecord(ev.second, c->stream));
+  return MI_DV_OK;
+}
+
 // the one-frame path's buffers hold a frame and a picture of these sizes (they only grow; the stream is idle between calls)
 int one_frame_buffers(mi_dv_ctx* c, size_t frame_bytes, size_t pic_bytes) {
   if (frame_bytes > c->cap_frame) {
@@ -276,6 +318,7 @@ struct Row {
   void (*rects)(uint32_t, uint32_t, uint32_t, Rect*);
   void (*hold_copy)(hipStream_t, const HoldChunkDev*, uint32_t, const uint64_t*, const int32_t*, uint8_t*, const uint8_t*,
                     unsigned long long*);
+  int (*encode)(mi_dv_ctx*, const void*, int, void*, int);  // the launch of k_dv_encode<Sys>
 };
 // a host function of its own: the kernels' S::place stays what dv_common.h makes of it
 template <class S>
@@ -296,7 +339,8 @@ void hold_copy_launch(hipStream_t st, const HoldChunkDev* chunks, uint32_t nitem
 template <class S>
 constexpr Row row(const char* frames, const char* what, bool says_apt, const char* expected) {
   return {S::kId, S::kFrameBytes, S::kPicBytes, {S::kW, S::kCW, S::kCW}, {S::kH, S::kCH, S::kCH}, S::kChans * S::kSeqs,
-          frames, what, expected, says_apt, launch<S>, place_thunk<S>, S::kSegments * 5, rects_thunk<S>, hold_copy_launch<S>};
+          frames, what, expected, says_apt, launch<S>, place_thunk<S>, S::kSegments * 5, rects_thunk<S>, hold_copy_launch<S>,
+          encode_launch<S>};
 }
 constexpr Row kSystems[] = {
     row<Sys525>("525/60", "525/60 25 Mbit/s DV frame", false, ""),
@@ -484,6 +528,20 @@ int decode_held(mi_dv_ctx* c, const Row& r, const char* who, const void* d_frame
   h.counted = true;
   return MI_DV_OK;
 }
+
+// ---- the encoder ----
+// n resident pictures of system r into n resident frames: every argument is checked before anything is launched
+int encode_batch(mi_dv_ctx* c, const Row& r, const char* who, const void* d_pics, int n, void* d_frames, int flags) {
+  if (!c || !d_pics || !d_frames || n <= 0) return fail(c, MI_DV_ERR_ARG, "%s: bad argument", who);
+  if (n > 65535) return fail(c, MI_DV_ERR_ARG, "%s: %d pictures; at most 65535 per call (split the batch)", who, n);
+  if (flags < 0 || flags > 3) return fail(c, MI_DV_ERR_ARG, "%s: flags %d; bit 0: 2-4-8 blocks, bit 1: classes", who, flags);
+  if (((uintptr_t)d_frames & 3u) || ((uintptr_t)d_pics & 7u))
+    return fail(c, MI_DV_ERR_ARG, "%s: d_frames must be 4-byte and d_pics 8-byte aligned", who);
+  const uintptr_t p0 = (uintptr_t)d_pics, p1 = p0 + (size_t)n * r.pic_bytes, q0 = (uintptr_t)d_frames, q1 = q0 + (size_t)n * r.frame_bytes;
+  if (p0 < q1 && q0 < p1) return fail(c, MI_DV_ERR_ARG, "%s: d_frames overlaps d_pics", who);
+  DVCHK(c, hipSetDevice(c->device));
+  return r.encode(c, d_pics, n, d_frames, flags);
+}
 }  // namespace
 
 extern "C" {
@@ -669,6 +727,71 @@ int mi_dv_decode_frame_held(mi_dv_ctx* c, int system, const uint8_t* frame, size
   }
   h.cur[id] ^= 1;
   h.kept = id;
+  return MI_DV_OK;
+}
+
+// ---- the encoder ----
+
+int mi_dv_encode_batch(mi_dv_ctx* c, int system, const void* d_pics, int n, void* d_frames, int flags) {
+  const Row* r = find(system);
+  if (!r) return fail(c, MI_DV_ERR_ARG, "mi_dv_encode_batch: unknown system %d", system);
+  return encode_batch(c, *r, "mi_dv_encode_batch", d_pics, n, d_frames, flags);
+}
+
+int mi_dv_encode_frame(mi_dv_ctx* c, int system, const uint8_t* const planes[3], const int strides[3], uint8_t* frame, size_t cap,
+                       int flags) {
+  const char* who = "mi_dv_encode_frame";
+  const Row* r = find(system);
+  if (!r) return fail(c, MI_DV_ERR_ARG, "%s: unknown system %d", who, system);
+  if (!c || !frame || !planes || !strides || !planes[0] || !planes[1] || !planes[2]) return fail(c, MI_DV_ERR_ARG, "%s: NULL argument", who);
+  if (cap < (size_t)r->frame_bytes)
+    return fail(c, MI_DV_ERR_ARG, "%s: room for %zu bytes: %s frames have %d", who, cap, r->frames, r->frame_bytes);
+  if (flags < 0 || flags > 3) return fail(c, MI_DV_ERR_ARG, "%s: flags %d; bit 0: 2-4-8 blocks, bit 1: classes", who, flags);
+  if (strides[0] < r->w[0] || strides[1] < r->w[1] || strides[2] < r->w[2]) return fail(c, MI_DV_ERR_ARG, "strides below the picture's width");
+  DVCHK(c, hipSetDevice(c->device));
+  int rc = one_frame_buffers(c, (size_t)r->frame_bytes, (size_t)r->pic_bytes);
+  if (rc != MI_DV_OK) return rc;
+  DVCHK(c, hipStreamSynchronize(c->stream));  // (the pinned picture is free)
+  uint8_t* dst = c->h_pic;
+  for (int pl = 0; pl < 3; pl++) {
+    const int w = r->w[pl], h = r->h[pl];
+    for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * w, planes[pl] + (size_t)y * strides[pl], (size_t)w);
+    dst += (size_t)w * h;
+  }
+  DVCHK(c, hipMemcpyAsync(c->d_pic, c->h_pic, (size_t)r->pic_bytes, hipMemcpyHostToDevice, c->stream));
+  rc = encode_batch(c, *r, who, c->d_pic, 1, c->d_frame, flags);
+  if (rc != MI_DV_OK) return rc;
+  DVCHK(c, hipMemcpyAsync(frame, c->d_frame, (size_t)r->frame_bytes, hipMemcpyDeviceToHost, c->stream));
+  DVCHK(c, hipStreamSynchronize(c->stream));
+  return MI_DV_OK;
+}
+
+int mi_dv_encode_times(mi_dv_ctx* c, float* total_ms, int* launches) {
+  if (!c || !total_ms || !launches) return MI_DV_ERR_ARG;
+  DVCHK(c, hipSetDevice(c->device));
+  DVCHK(c, hipStreamSynchronize(c->stream));
+  float sum = 0.f;
+  for (auto& e : c->enc_ev_used) {
+    float ms = 0.f;
+    DVCHK(c, hipEventElapsedTime(&ms, e.first, e.second));
+    sum += ms;
+  }
+  *total_ms = sum;
+  *launches = (int)c->enc_ev_used.size();
+  for (auto& e : c->enc_ev_used) c->ev_free.push_back(e);
+  c->enc_ev_used.clear();
+  return MI_DV_OK;
+}
+
+int mi_dv_encode_stats(mi_dv_ctx* c, long long qno_hist[16], long long* dropped) {
+  if (!c || !qno_hist || !dropped) return MI_DV_ERR_ARG;
+  DVCHK(c, hipSetDevice(c->device));
+  DVCHK(c, hipStreamSynchronize(c->stream));
+  unsigned long long v[kEncStats];
+  DVCHK(c, hipMemcpyAsync(v, c->d_enc_stats, sizeof v, hipMemcpyDeviceToHost, c->stream));
+  DVCHK(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < 16; i++) qno_hist[i] = (long long)v[i];
+  *dropped = (long long)v[16];
   return MI_DV_OK;
 }
 

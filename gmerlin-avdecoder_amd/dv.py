@@ -1,4 +1,4 @@
-"""ctypes view of include/mi_dv.h (libmi_dv.so, the DV decoder: 525/60 4:1:1, 625/50 4:2:0 and 625/50 4:1:1 at
+"""ctypes view of include/mi_dv.h (libmi_dv.so, the DV decoder and encoder: 525/60 4:1:1, 625/50 4:2:0 and 625/50 4:1:1 at
 25 Mbit/s, both line systems in 4:2:2 at 50 Mbit/s).  No CPU path: without the library or a gfx950 device construction raises MiDvError with
 the library's own message."""
 import ctypes as C
@@ -25,7 +25,8 @@ EXPORTS = ["mi_dv_device_count", "mi_dv_create", "mi_dv_destroy", "mi_dv_last_er
            "mi_dv_h2d", "mi_dv_d2h", "mi_dv_sync", "mi_dv_decode_batch", "mi_dv_kernel_times", "mi_dv_decode_frame",
            "mi_dv_copy_tables", "mi_dv_system_of", "mi_dv_decode_batch_sys", "mi_dv_decode_frame_sys", "mi_dv_mb_place",
            "mi_dv_profile_of", "mi_dv_kind_of", "mi_dv_mb_rects", "mi_dv_held_macroblocks", "mi_dv_decode_batch_held",
-           "mi_dv_hold_stats", "mi_dv_hold_times", "mi_dv_decode_frame_held", "mi_dv_hold_reset"]
+           "mi_dv_hold_stats", "mi_dv_hold_times", "mi_dv_decode_frame_held", "mi_dv_hold_reset", "mi_dv_encode_batch",
+           "mi_dv_encode_frame", "mi_dv_encode_times", "mi_dv_encode_stats"]
 STA_ERRORS = 0x8080  # the default mask of held macroblocks: STA 0111 and 1111 (include/mi_dv.h: MI_DV_STA_ERRORS)
 _LIB = None
 u8p = C.POINTER(C.c_uint8)
@@ -81,6 +82,10 @@ def load():
     L.mi_dv_decode_frame_held.argtypes = [vp, C.c_int, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int), C.c_uint,
                                           C.POINTER(C.c_int)]
     L.mi_dv_hold_reset.argtypes = [vp]
+    L.mi_dv_encode_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    L.mi_dv_encode_frame.argtypes = [vp, C.c_int, C.POINTER(u8p), C.POINTER(C.c_int), u8p, C.c_size_t, C.c_int]
+    L.mi_dv_encode_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    L.mi_dv_encode_stats.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     _LIB = L
     return L
 
@@ -299,6 +304,53 @@ class MiDv:
         ms, n = C.c_float(), C.c_int()
         self._chk(self.L.mi_dv_hold_times(self.c, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    # ---- the encoder (include/mi_dv.h; parity unpinned like the decoder) ----
+    def encode_batch(self, system, d_pics, n, d_frames, flags=3):
+        """n resident pictures of the system -> n resident DIF frames, queued on the instance's stream.  flags: bit 0 lets
+        blocks take the 2-4-8 transform, bit 1 gives them classes by content"""
+        self._chk(self.L.mi_dv_encode_batch(self.c, system, d_pics, n, d_frames, flags))
+
+    def encode_frames(self, pics, system, flags=3):
+        """host pictures (n x the system's picture bytes, uint8) -> host frames (n x its frame bytes), through the batch path"""
+        fb, pb, _ = geometry(system)
+        pics = np.ascontiguousarray(pics, np.uint8).reshape(-1, pb)
+        n = pics.shape[0]
+        dp, df = self.alloc(n * pb), self.alloc(n * fb)
+        try:
+            self.h2d(dp, pics)
+            self.encode_batch(system, dp, n, df, flags)
+            self.sync()
+            return self.d2h(df, n * fb).reshape(n, fb)
+        finally:
+            self.free(dp)
+            self.free(df)
+
+    def encode_frame(self, planes, system, strides=None, flags=3, cap=None):
+        """one picture from three host planes of the given strides (default: the system's plane widths) -> one host frame;
+        cap: the room offered for it (default: the system's frame bytes)"""
+        fb, _, planes_wh = geometry(system)
+        if strides is None:
+            strides = tuple(w for w, _ in planes_wh)
+        planes = [np.ascontiguousarray(p, np.uint8) for p in planes]
+        cap = fb if cap is None else cap
+        frame = np.zeros(max(cap, 1), np.uint8)
+        pp = (u8p * 3)(*[p.ctypes.data_as(u8p) for p in planes])
+        st = (C.c_int * 3)(*strides)
+        self._chk(self.L.mi_dv_encode_frame(self.c, system, pp, st, frame.ctypes.data_as(u8p), cap, flags))
+        return frame[:fb]
+
+    def encode_times(self):
+        """(total milliseconds, launches) of k_dv_encode since the last call; kernel_times keeps k_dv_decode's"""
+        ms, n = C.c_float(), C.c_int()
+        self._chk(self.L.mi_dv_encode_times(self.c, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def encode_stats(self):
+        """(segments per chosen quantisation number [16], levels the overflow rule dropped) of the last encoded batch"""
+        hist, dropped = (C.c_longlong * 16)(), C.c_longlong()
+        self._chk(self.L.mi_dv_encode_stats(self.c, hist, C.byref(dropped)))
+        return np.array(hist[:], np.int64), dropped.value
 
     def close(self):
         if self.c:

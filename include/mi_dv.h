@@ -1,5 +1,5 @@
 /*
- * mi_dv.h — C ABI of the MI355X (gfx950) DV video decoder.  Five systems.  At 25 Mbit/s: 525/60 (NTSC), 120,000-byte
+ * mi_dv.h — C ABI of the MI355X (gfx950) DV video decoder (and, at the end, encoder).  Five systems.  At 25 Mbit/s: 525/60 (NTSC), 120,000-byte
  * DIF frames in, 720 x 480 4:1:1 pictures out; 625/50 (PAL) in the IEC 4:2:0 profile, 144,000-byte DIF frames in,
  * 720 x 576 4:2:0 pictures out; and 625/50 in the DVCPRO 4:1:1 profile, 144,000-byte DIF frames in, 720 x 576 4:1:1
  * pictures out.  At 50 Mbit/s ("DVCPRO50", two DIF channels): 525/60, 240,000-byte frames in, 720 x 480
@@ -174,6 +174,32 @@ int mi_dv_decode_frame_held(mi_dv_ctx *c, int system, const uint8_t *frame, size
                             const int strides[3], unsigned sta_mask, int *held);
 /* Forget the kept picture (a decoder's .resync: after a seek the frame before is not the stream's previous picture). */
 int mi_dv_hold_reset(mi_dv_ctx *c);
+
+/* ---- the encoder: pictures on the device -> DIF frames of any of the five systems ----
+ *
+ * PARITY UNPINNED like the decoder: the frames follow this repository's reading of the format (oracle/dv_oracle.c) and
+ * the integer statement tests/dvenc.py, which the kernel reproduces bit for bit; this library decodes them, and so does
+ * the oracle.  Nothing here was compared with another DV implementation.  Every frame is complete: the video segments
+ * (forward transforms, quantisation by the largest quantisation number at which a segment fits its 2,680 AC bits, the
+ * three passes), block ids with the channel bit, DSF, the system's default APT and VAUX stype (mi_dv_kind_of answers the
+ * system), zeros everywhere else: no audio, subcode or VAUX content.  flags: bit 0 lets a block take the 2-4-8 transform
+ * where its two fields differ, bit 1 gives every block a class by its content (clear: class 0). */
+
+/* n pictures of the system's size, resident in device memory and back to back (the layout mi_dv_decode_batch_sys
+ * writes), -> n frames of the system's size.  The alignment and batch rules of mi_dv_decode_batch_sys: d_pics 8-byte,
+ * d_frames 4-byte aligned, at most 65535 per call.  Queued on the instance's stream; pair with mi_dv_sync.  MI_DV_ERR_ARG,
+ * with nothing launched, for an unknown system, n out of range, NULL, misaligned or overlapping buffers, flags above 3. */
+int mi_dv_encode_batch(mi_dv_ctx *c, int system, const void *d_pics, int n, void *d_frames, int flags);
+/* One picture from the caller's planes (Y, Cb, Cr) with the caller's strides into `cap` bytes of host memory.
+ * Synchronous.  MI_DV_ERR_ARG for a cap below the system's frame bytes, strides below the planes' widths, flags above 3,
+ * an unknown system. */
+int mi_dv_encode_frame(mi_dv_ctx *c, int system, const uint8_t *const planes[3], const int strides[3], uint8_t *frame,
+                       size_t cap, int flags);
+/* Device time of k_dv_encode since the last call, as mi_dv_kernel_times, which keeps counting k_dv_decode alone. */
+int mi_dv_encode_times(mi_dv_ctx *c, float *total_ms, int *launches);
+/* Of the last encoded batch: the video segments per chosen quantisation number, and the levels the overflow rule
+ * dropped (a segment that does not fit at quantisation number 0 loses last levels of its longest blocks).  Synchronises. */
+int mi_dv_encode_stats(mi_dv_ctx *c, long long qno_hist[16], long long *dropped);
 
 #ifdef __cplusplus
 }
