@@ -115,6 +115,15 @@ struct SpecIndex {
   DevBuf<uint2> fix;              // [walkers]: (walker, byte to start from) of the chunks to walk again
   DevBuf<uint8_t> flag;           // [walkers + 64]: 1 = on that list in this launch
   DevBuf<uint32_t> nfix;
+  // runs of chunks (spec_run_length(); run_s == 1: one walker per chunk and none of these)
+  uint32_t run_s = 1;             // chunks a run walker takes at most
+  uint64_t nruns = 0;
+  std::vector<SpecRunDev> h_runs;
+  std::vector<uint32_t> h_rbase;  // [frames + 1]: a packet's first run
+  DevBuf<SpecRunDev> runs;        // [nruns]
+  DevBuf<uint32_t> rbase;         // [frames + 1]
+  DevBuf<uint32_t> runrec;        // the run walkers' start bits: spec_bits_words_t(nruns, spec_run_tiles(run_s)) dwords
+  DevBuf<uint32_t> brow;          // [walkers]: whose bits a chunk's are (SpecRunArgs)
   // sized by the frames
   DevBuf<uint32_t> base;          // [frames + 1]
   DevBuf<uint32_t> ok;            // [frames]: 1 = the packet's index is proven
@@ -373,6 +382,19 @@ int plan_alloc_chunks(mi_rtj_plan* p) {
     if (sp.n >= 0x7FFFFFFFull) sp.on = false;  // walker numbers are 32-bit
   }
   if (!sp.on) return MI_RTJ_OK;
+  // runs: the short lead only (plans forced to a longer one keep a walker per chunk), by the number of chunks or
+  // MI_RTJ_SPEC_RUN; plans whose blocks all parse alike (lb8 == cb8, the 10-instruction byte step) take them only when forced
+  sp.run_s = p->sw.spec_mode == 3 || p->sw.spec_mode == 4 || (p->one_block_type && p->sw.spec_run < 1)
+                 ? 1u
+                 : spec_run_length(sp.n, p->sw.spec_run);
+  sp.h_runs.clear();
+  sp.h_rbase.assign(1, 0u);
+  if (sp.run_s > 1u)
+    for (size_t i = 0; i < p->h_frames.size(); i++) {
+      spec_packet_runs((uint32_t)i, sp.h_base[i], sp.h_base[i + 1] - sp.h_base[i], sp.run_s, sp.h_runs);
+      sp.h_rbase.push_back((uint32_t)sp.h_runs.size());
+    }
+  sp.nruns = sp.h_runs.size();
   const uint64_t frames = p->h_frames.size();
   // (rec: whole waves of walkers, + a spare walker for idle lanes; flag: the walkers zero [0, n) per launch; nfix and, below,
   // state are made once; ok starts as "nothing proven yet" for mi_rtj_plan_spec_stats)
@@ -388,6 +410,16 @@ int plan_alloc_chunks(mi_rtj_plan* p) {
       return rc;
     HIPCHK(c, hipMemsetAsync(sp.todo + frames + 1, 0, sizeof(uint32_t), s));
     if ((rc = sp.state.grow(c, kSpecStWords, s, 0, true))) return rc;
+  }
+  if (sp.run_s > 1u) {
+    const uint64_t words = spec_bits_words_t(sp.nruns, spec_run_tiles(sp.run_s));
+    if ((sp.nruns > sp.runs.cap && ((rc = dev_release(c, s, sp.runs)) || (rc = sp.runs.grow(c, sp.nruns, s)))) ||
+        (words > sp.runrec.cap && ((rc = dev_release(c, s, sp.runrec)) || (rc = sp.runrec.grow(c, words, s)))) ||
+        (sp.n > sp.brow.cap && ((rc = dev_release(c, s, sp.brow)) || (rc = sp.brow.grow(c, sp.n, s)))) ||
+        (sp.h_rbase.size() > sp.rbase.cap && ((rc = dev_release(c, s, sp.rbase)) || (rc = sp.rbase.grow(c, sp.h_rbase.size(), s)))))
+      return rc;
+    HIPCHK(c, hipMemcpyAsync(sp.rbase, sp.h_rbase.data(), sizeof(uint32_t) * sp.h_rbase.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(sp.runs, sp.h_runs.data(), sizeof(SpecRunDev) * sp.nruns, hipMemcpyHostToDevice, s));
   }
   HIPCHK(c, hipMemcpyAsync(sp.chunks, sp.h_chunks.data(), sizeof(SpecChunkDev) * sp.n, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(sp.base, sp.h_base.data(), sizeof(uint32_t) * sp.h_base.size(), hipMemcpyHostToDevice, s));
@@ -433,7 +465,11 @@ int plan_launch(mi_rtj_plan* p, const void* d_stream, void* d_out, int what = kL
     const bool spec = p->spec.on && !p->sw.serial_index;
     if (spec) {
       rows = std::min<unsigned>(rows, kSpecFallbackRows);
-      const SpecGrids g{dim3((unsigned)((p->spec.n + 63) / 64)), dim3(p->n), dim3(kSpecRepairGrid)};
+      // a lane per chunk, or per run where nothing but the short lead can be asked for (with a policy the longer leads
+      // still walk a lane per chunk, and the policy's choice is the device's to know: k_spec_walk_any)
+      const int sm = p->sw.spec_mode;
+      const uint64_t lanes = p->spec.run_s > 1u && sm == 1 ? p->spec.nruns : p->spec.n;
+      const SpecGrids g{dim3((unsigned)((lanes + 63) / 64)), dim3(p->n), dim3(kSpecRepairGrid)};
       if ((rc = stage_spec_index(L, g)) != MI_RTJ_OK) return rc;
     }
     ExactGrids g;

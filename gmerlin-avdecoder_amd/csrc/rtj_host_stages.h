@@ -88,13 +88,23 @@ struct WalkArgs {
   uint32_t *recbits, *nrec, *wstart;
   uint2* hand;
   SpecReset rs;
+  SpecRunArgs ra;  // a plan with runs (ra.runs): the short lead walks a lane per run, rtj_spec_kernels.h
 };
 #define WALK(kernel, ...) \
-  hipLaunchKernelGGL(kernel, grid, dim3(64), 0, s, a.frames, a.chunks, a.total, a.stream, a.lut, a.recbits, a.nrec, a.wstart, a.hand, a.rs, ##__VA_ARGS__)
+  hipLaunchKernelGGL(kernel, grid, dim3(64), 0, s, a.frames, a.chunks, a.total, a.stream, a.lut, a.recbits, a.nrec, a.wstart, a.hand, a.rs, a.ra, ##__VA_ARGS__)
 void launch_spec_walk(bool two_types, int spec_mode, uint32_t* state, dim3 grid, hipStream_t s, const WalkArgs& a) {
+  const bool runs = a.ra.runs != nullptr;
   if (state) {
-    if (!two_types) WALK((k_spec_walk_any<false>), state);
-    else WALK((k_spec_walk_any<true>), state);
+    if (!two_types) {
+      if (runs) WALK((k_spec_walk_any<false, true>), state);
+      else WALK((k_spec_walk_any<false>), state);
+    } else {
+      if (runs) WALK((k_spec_walk_any<true, true>), state);
+      else WALK((k_spec_walk_any<true>), state);
+    }
+  } else if (runs) {  // (forced, MI_RTJ_SPEC=1 with MI_RTJ_SPEC_RUN: the short lead)
+    if (!two_types) WALK((k_spec_walk<false, kSpecLead, true>));
+    else WALK((k_spec_walk<true, kSpecLead, true>));
   } else if (!two_types) {
     if (spec_mode == 1) WALK((k_spec_walk<false, kSpecLead>));
     if (spec_mode == 3) WALK((k_spec_walk<false, kSpecLeadLong>));
@@ -172,19 +182,25 @@ int stage_spec_index(Launch& L, const SpecGrids& g) {
   L.state = no_policy ? nullptr : s.state.p;
   L.ntodo = s.todo;
   L.todo = s.todo + 1;
+  const SpecRunArgs ra = s.run_s > 1u ? SpecRunArgs{s.runs.p, (uint32_t)s.nruns, s.run_s, s.runrec.p, s.rbase.p, s.brow.p}
+                                         : SpecRunArgs{nullptr, 0u, 1u, nullptr, nullptr, nullptr};
   STAGE_CHK(L.clk.begin());
   launch_spec_walk(!p->one_block_type, mode, L.state, g.walk, L.is,
-                   WalkArgs{p->d_frames, s.chunks, (uint32_t)s.n, L.st, lut, s.rec, s.nrec, s.wstart, s.hand, SpecReset{s.nfix, s.todo, s.flag}});
+                   WalkArgs{p->d_frames, s.chunks, (uint32_t)s.n, L.st, lut, s.rec, s.nrec, s.wstart, s.hand, SpecReset{s.nfix, s.todo, s.flag}, ra});
   STAGE_CHK(L.clk.end(MI_RTJ_K_SPEC_WALK));
   STAGE_CHK(L.clk.begin());
   // first pass; walkers that had not fallen into step are walked again from a known block start; second pass over the
   // packets concerned (both return at once when there is nothing to repair)
   for (int pass = 1; pass <= 2; pass++) {
-    hipLaunchKernelGGL(k_spec_verify, g.verify, dim3(kSpecVerThreads), 0, L.is, p->d_frames, s.base, lut, s.rec, s.nrec, L.blk,
-                       s.ok, s.todo + 1, s.todo, L.state, s.wstart, s.hand, s.fix, s.nfix, s.flag, pass);
+    if (ra.runs)
+      hipLaunchKernelGGL(k_spec_verify<true>, g.verify, dim3(kSpecVerThreads), 0, L.is, p->d_frames, s.base, lut, s.rec, s.nrec, L.blk,
+                         s.ok, s.todo + 1, s.todo, L.state, s.wstart, s.hand, s.fix, s.nfix, s.flag, pass, ra);
+    else
+      hipLaunchKernelGGL(k_spec_verify<false>, g.verify, dim3(kSpecVerThreads), 0, L.is, p->d_frames, s.base, lut, s.rec, s.nrec, L.blk,
+                         s.ok, s.todo + 1, s.todo, L.state, s.wstart, s.hand, s.fix, s.nfix, s.flag, pass, ra);
     if (pass == 1)
       hipLaunchKernelGGL(k_spec_repair, g.repair, dim3(64), 0, L.is, p->d_frames, s.chunks, L.st, lut, s.rec, s.nrec, s.wstart,
-                         s.hand, s.fix, s.nfix, s.flag, (uint32_t)s.n, L.state);
+                         s.hand, s.fix, s.nfix, s.flag, (uint32_t)s.n, L.state, ra.brow);
   }
   STAGE_CHK(L.clk.end(MI_RTJ_K_SPEC_VERIFY));
   if (L.state)

@@ -22,8 +22,8 @@ static inline const char* exp_env(const char* name) {
 }
 
 // Who makes the plan decides which switches it honours (DESIGN.md has the same table):
-//   batch (mi_rtj_plan_create)    MI_RTJ_INDEX, _EMIT, _SPEC, _DEC_SLOTS, _ROTATE, _SERIAL_MIN, _SPLIT, _OVERLAP
-//   one packet (mi_rtj_decode*)   MI_RTJ_INDEX, _EMIT, _SPEC; the rest at their defaults
+//   batch (mi_rtj_plan_create)    MI_RTJ_INDEX, _EMIT, _SPEC, _SPEC_RUN, _DEC_SLOTS, _ROTATE, _SERIAL_MIN, _SPLIT, _OVERLAP
+//   one packet (mi_rtj_decode*)   MI_RTJ_INDEX, _EMIT, _SPEC, _SPEC_RUN; the rest at their defaults
 //   session slot, session group   MI_RTJ_INDEX, _EMIT; no speculation (one or a handful of packets per launch: a lone
 //                                 walker takes longer than all of the exact index); the rest at their defaults
 enum PlanKind { kPlanBatch = 0, kPlanOnePacket, kPlanSessionSlot, kPlanSessionGroup };
@@ -33,6 +33,8 @@ struct PlanSwitches {
   bool emit_walk = false;      // MI_RTJ_EMIT=walk: per-chunk re-walk instead of the length tables
   int spec_mode = -1;          // MI_RTJ_SPEC: 0 never, 1 / 3 / 4 always with the short / long / very long lead (no policy),
                                // 2 whatever the batch size, otherwise by batch size
+  int spec_run = 0;            // MI_RTJ_SPEC_RUN (A/B, tests): 1 .. 4 = chunks a walker of the short lead walks behind one lead,
+                               // whatever the launch's size; otherwise by the number of chunks (spec_run_length())
   uint32_t dec_slots = 0;      // MI_RTJ_DEC_SLOTS (A/B): k_decode waves per part, 0 = decode_slots()
   int rotate = -1;             // MI_RTJ_ROTATE: 1 / 0 = a k_decode wave takes all three parts of its groups / one part; -1 = by batch size
   uint32_t serial_min = 4096;  // MI_RTJ_SERIAL_MIN: to-do lists from this many packets on go to the serial walker (0: never)
@@ -53,6 +55,7 @@ static inline PlanSwitches plan_switches_from_env(PlanKind kind) {
     return s;
   }
   if ((v = getenv("MI_RTJ_SPEC"))) s.spec_mode = atoi(v);
+  if ((v = getenv("MI_RTJ_SPEC_RUN"))) s.spec_run = atoi(v);
   if (kind != kPlanBatch) return s;
   if ((v = getenv("MI_RTJ_DEC_SLOTS"))) s.dec_slots = (uint32_t)atoi(v);
   if ((v = getenv("MI_RTJ_ROTATE"))) s.rotate = atoi(v) != 0;

@@ -14,6 +14,8 @@
 //                  byte (round 3; 16-bit positions through an LDS ring before).
 //                  64 chunks advance in lockstep per wave: 15 vector instructions per byte for 64
 //                  streams, against ~20 per BLOCK POSITION AND TYPE in k_index_summarize.
+//                  In launches large enough to fill the device without it, one lane per RUN of up to four chunks behind
+//                  ONE lead (SpecRunDev, spec_run_length): the records stay per chunk.
 //   k_spec_verify  per packet: the last (macro)block start a walker saw in its lead, i.e. before its
 //                  chunk, must be the last one its predecessor saw before the end of its span, which is
 //                  the same byte (the walkers report both); chunk 0 starts at byte 0.  Two walkers that stand on the same byte in the same
@@ -70,40 +72,52 @@ constexpr int kSpecTile = 128;    // bytes per lane fetched at a time (one cache
 // write per byte, flush checks every 16 bytes, 4 KB reserved per walker and a cap of 2048 blocks per span; the bits
 // cost k_spec_verify a rank-to-position step per chunk (a popcount scan over at most 112 dwords) and need no cap.
 constexpr int kSpecTilesMax = kSpecSpan / kSpecTile;  // tiles of the longest span: a walker's bits are 16 bytes per tile
-__host__ __device__ constexpr size_t spec_bits_words(uint64_t walkers) {  // dwords of the bit buffer (+ a spare walker)
-  return (size_t)((walkers + 1 + 63) / 64) * (size_t)kSpecTilesMax * 64u * 4u;
+// The same layout serves two kinds of walker: one per chunk (`tiles` = kSpecTilesMax, whatever the lead), and one per RUN
+// of up to S chunks behind one short lead (`tiles` = spec_run_tiles(S), below, in a buffer of their own).
+__host__ __device__ constexpr size_t spec_bits_words_t(uint64_t walkers, uint32_t tiles) {  // dwords of a bit buffer (+ a spare walker)
+  return (size_t)((walkers + 1 + 63) / 64) * (size_t)tiles * 64u * 4u;
 }
 // dword k (positions 32 k .. 32 k + 31) of a walker's bits, in dwords from the start of the buffer: [wave of walkers]
 // [tile][lane][4].  (A layout with each walker's bits contiguous, the walkers transposing four tiles at a time through
 // LDS, was tried at the end of round 3 and did not pass the GPU tests; it is not in the tree.)
-__host__ __device__ constexpr size_t spec_bits_dword(uint32_t walker, uint32_t k) {
-  return (((size_t)(walker >> 6) * (size_t)kSpecTilesMax + (k >> 2)) * 64u + (walker & 63u)) * 4u + (k & 3u);
+__host__ __device__ constexpr size_t spec_bits_dword_t(uint32_t walker, uint32_t k, uint32_t tiles) {
+  return (((size_t)(walker >> 6) * (size_t)tiles + (k >> 2)) * 64u + (walker & 63u)) * 4u + (k & 3u);
 }
+__host__ __device__ constexpr size_t spec_bits_words(uint64_t walkers) { return spec_bits_words_t(walkers, (uint32_t)kSpecTilesMax); }
+__host__ __device__ constexpr size_t spec_bits_dword(uint32_t walker, uint32_t k) {
+  return spec_bits_dword_t(walker, k, (uint32_t)kSpecTilesMax);
+}
+// Runs of chunks: in launches that keep the device full without it, one walker lane walks up to S consecutive chunks of
+// a packet behind ONE short lead, so the lead is parsed once per run instead of once per chunk: (lead + S * chunk) /
+// (S * chunk) = 1.375, 1.19, 1.125, 1.09 for S = 1 .. 4.  The walker's bits are those of one long span.
+constexpr int kSpecRunMax = 4;
+__host__ __device__ constexpr uint32_t spec_run_tiles(uint32_t S) { return (uint32_t)(kSpecLead + (int)S * kSpecChunk) / (uint32_t)kSpecTile; }
 // The layout's bounds, checked where the layout is defined: every (walker, dword) of a
 // launch of `walkers` walkers — the idle lanes of the last wave stand in for the spare walker `walkers` — lies inside
-// spec_bits_words(walkers), and no two of them share a dword.  Evaluated at compile time for walker counts on both
-// sides of a wave boundary; a change of either function that breaks this does not build.
-constexpr bool spec_bits_layout_ok(uint32_t walkers) {
-  const size_t words = spec_bits_words(walkers);
+// spec_bits_words_t(walkers, tiles), and no two of them share a dword.  Evaluated at compile time for walker counts on
+// both sides of a wave boundary, for the chunk walkers' tiles and for those of every run length; a change of either
+// function that breaks this does not build.
+constexpr bool spec_bits_layout_ok(uint32_t walkers, uint32_t tiles = (uint32_t)kSpecTilesMax) {
+  const size_t words = spec_bits_words_t(walkers, tiles);
   const uint32_t rows = ((walkers + 1u + 63u) / 64u) * 64u;  // walker rows the kernels may touch (whole waves)
-  const uint32_t kmax = (uint32_t)kSpecTilesMax * 4u;
+  const uint32_t kmax = tiles * 4u;
   // (sampled, to stay inside the compiler's constexpr step limit: every walker row at the first and last dwords of its
   // first, second and last tile; every dword of the first, 64th and last row)
   size_t top = 0;
   for (uint32_t w = 0; w < rows; w++) {
     const uint32_t ks[6] = {0u, 3u, 4u, 7u, kmax - 4u, kmax - 1u};
     for (uint32_t k : ks) {
-      const size_t d = spec_bits_dword(w, k);
+      const size_t d = spec_bits_dword_t(w, k, tiles);
       if (d >= words) return false;
-      if (w + 1u < rows && d == spec_bits_dword(w + 1u, k)) return false;
+      if (w + 1u < rows && d == spec_bits_dword_t(w + 1u, k, tiles)) return false;
       top = d > top ? d : top;
     }
   }
   const uint32_t ws[3] = {0u, rows > 64u ? 64u : rows - 1u, rows - 1u};
   for (uint32_t w : ws)
     for (uint32_t k = 0; k < kmax; k++) {
-      const size_t d = spec_bits_dword(w, k);
-      if (d >= words || (k + 1u < kmax && d == spec_bits_dword(w, k + 1u))) return false;
+      const size_t d = spec_bits_dword_t(w, k, tiles);
+      if (d >= words || (k + 1u < kmax && d == spec_bits_dword_t(w, k + 1u, tiles))) return false;
       top = d > top ? d : top;
     }
   return top + 1u == (size_t)rows * kmax && top + 1u <= words;  // dense: the last dword of the last row is the buffer's last
@@ -111,6 +125,13 @@ constexpr bool spec_bits_layout_ok(uint32_t walkers) {
 static_assert(spec_bits_layout_ok(1) && spec_bits_layout_ok(63) && spec_bits_layout_ok(64) && spec_bits_layout_ok(65) &&
                   spec_bits_layout_ok(200),
               "a walker's start bits leave the buffer");
+constexpr bool spec_run_layouts_ok() {
+  for (uint32_t S = 1; S <= (uint32_t)kSpecRunMax; S++)
+    for (uint32_t w : {1u, 63u, 64u, 65u, 200u})
+      if (!spec_bits_layout_ok(w, spec_run_tiles(S))) return false;
+  return true;
+}
+static_assert(spec_run_layouts_ok(), "a run walker's start bits leave the buffer");
 constexpr uint64_t kSpecMinWalkers = 40000;  // below this (~100 MB of packets) the exact kernels index a batch faster:
                                             // a walker is one lane and runs ~0.35 ms whatever the batch (host policy)
 constexpr int kSpecRingRow = 64 + 16;       // LDS bytes per lane: the start bits of the last four tiles (512 bytes of
@@ -124,6 +145,47 @@ static_assert(kSpecLeadLong >= kSpecLead && kSpecLeadLong % kSpecTile == 0 && kS
 struct SpecChunkDev {
   uint32_t frame;  // index into the plan's frames
   uint32_t c;      // chunk number within the packet
+};
+// A run: n <= S consecutive chunks of one packet that one walker lane walks behind one lead.  Runs never cross a packet;
+// a packet's first run starts at byte 0, its last one is the shorter one.
+struct SpecRunDev {
+  uint32_t frame;  // index into the plan's frames
+  uint32_t c;      // the run's first chunk, numbered within the packet
+  uint32_t n;      // chunks of the run, 1 .. S
+  uint32_t chunk;  // the first chunk's number in the plan's chunk list: per-chunk records [chunk, chunk + n) are the run's
+};
+// the runs of one packet of nsc chunks whose first is number chunk0 of the plan's list (the host, when the plan is made)
+template <class Out>
+inline void spec_packet_runs(uint32_t frame, uint32_t chunk0, uint32_t nsc, uint32_t S, Out& out) {
+  for (uint32_t c = 0; c < nsc; c += S) out.push_back(SpecRunDev{frame, c, nsc - c < S ? nsc - c : S, chunk0 + c});
+}
+// Which S a plan takes.  The compiled walkers take 94 vector registers where all blocks parse alike and 97 where luma
+// and chroma differ (k_spec_walk_any, either kind of plan; .vgpr_count of the code object): allocated in eights out of a
+// SIMD's 512 that is 5 and 4 waves per SIMD, 5,120 and 4,096 resident waves on 256 CUs, and the 5 KB of LDS a wave takes
+// would allow 8.  A GENERATION is counted with the larger figure: 327,680 walker lanes.  All walkers of a launch take the
+// same number of byte steps, so the last, partly filled generation is lost time, up to 1 / generations of the launch,
+// and a run of S chunks makes S times fewer, S times longer walkers.  A plan takes the longest run that still leaves
+// kSpecRunMinGens full generations, and one walker per chunk under 2 * kSpecRunMinGens generations, as before.  The
+// bench's 4,714,741 chunks at 5 (4) waves per SIMD: 14.4 -> 15 (18.0 -> 18) generations at S = 1, 7.2 -> 8 (9.0 -> 9)
+// at S = 2, 4.8 -> 5 (6.0 -> 6) at S = 3, 3.6 -> 4 (4.5 -> 5) at S = 4: S = 3.
+constexpr uint64_t kSpecGeneration = 256ull * 4ull * 5ull * 64ull;
+constexpr uint64_t kSpecRunMinGens = 4;
+__host__ __device__ constexpr uint32_t spec_run_length(uint64_t chunks, int forced) {
+  if (forced >= 1) return (uint32_t)(forced < kSpecRunMax ? forced : kSpecRunMax);
+  uint32_t S = 1;
+  for (uint32_t k = 2; k <= (uint32_t)kSpecRunMax; k++)
+    if (chunks / k >= kSpecRunMinGens * kSpecGeneration) S = k;
+  return S;
+}
+// What the kernels of a plan with runs get besides the per-chunk records (all null / 0 in a plan without):
+struct SpecRunArgs {
+  const SpecRunDev* runs;
+  uint32_t nruns;
+  uint32_t S;         // the plan's run length: the run walkers' bits are spec_run_tiles(S) tiles per walker
+  uint32_t* runbits;  // the run walkers' start bits, spec_bits_words_t(nruns, spec_run_tiles(S)) dwords
+  const uint32_t* rbase;  // [frames + 1]: the number of a packet's first run (its runs are S chunks each but the last)
+  uint32_t* brow;     // [chunks]: where a chunk's start bits are: 0 = in its own row of the chunk walkers' buffer (a walker
+                      // of its own wrote them, or k_spec_repair), r + 1 = in run walker r's, relative to that run's first byte
 };
 constexpr int kSpecFallbackRows = 64;
 constexpr int kSpecRepairGrid = 4096;   // waves of k_spec_repair (they loop over the list of chunks to walk again)
@@ -208,24 +270,43 @@ struct SpecReset {
   uint8_t* fixflag;
 };
 
-template <bool PHASE, int LEAD>
+// RUNS: the lane walks run g of the plan's run list — ra.S chunks at most, of which the lane's own run has `nch` — and
+// leaves the per-chunk records (nrec, wstart, hand) of each of them as a walker of that chunk alone would, but relative
+// to the RUN's first byte: at every chunk boundary inside the run, the pair it records today at its chunk's start and
+// end.  The proof (k_spec_verify) keeps its unit; a boundary inside a run holds by construction.
+template <bool PHASE, int LEAD, bool RUNS = false>
 __device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, const FrameDev* __restrict__ frames,
                                                const SpecChunkDev* __restrict__ chunks, uint32_t total,
                                                const uint8_t* __restrict__ stream, const QTab* __restrict__ lut,
                                                uint32_t* __restrict__ recbits, uint32_t* __restrict__ nrec,
                                                uint32_t* __restrict__ wstart, uint2* __restrict__ hand,
-                                               const SpecReset rs) {
+                                               const SpecReset rs, const SpecRunArgs ra) {
   constexpr int kSpan = LEAD + kSpecChunk;
+  constexpr int kChunkTiles = kSpecChunk / kSpecTile;
   static_assert(kSpan % kSpecTile == 0 && kSpan < 65536, "walker span: whole tiles, 16-bit positions");
+  static_assert(!RUNS || LEAD == kSpecLead, "runs are walked behind the short lead only");
+  static_assert(kSpecLead + kSpecRunMax * kSpecChunk < 65536, "a run's span: 16-bit positions and block counts");
   const int lane = threadIdx.x;
   const uint32_t g = blockIdx.x * 64u + (uint32_t)lane;
+  if (RUNS) total = ra.nruns;  // (the grid may be sized for a walker per chunk: waves without a run leave)
+  if (RUNS && blockIdx.x * 64u >= total) return;
   const bool act = g < total;
-  if (act) rs.fixflag[g] = 0;
   if (g == 0u) {
     *rs.nfix = 0u;
     *rs.ntodo = 0u;
   }
-  const SpecChunkDev sc = chunks[act ? g : total - 1u];  // idle lanes shadow the last chunk and store nothing
+  SpecChunkDev sc;
+  uint32_t nch = 1u, chunk0 = g;  // chunks of the lane's run (idle lanes: none), and the first one's number in the plan
+  if constexpr (RUNS) {
+    const SpecRunDev run = ra.runs[act ? g : total - 1u];  // idle lanes shadow the last run and record nothing
+    sc = SpecChunkDev{run.frame, run.c};
+    nch = act ? run.n : 0u;
+    chunk0 = run.chunk;
+  } else {
+    if (act) rs.fixflag[g] = 0;
+    if (act && ra.brow) ra.brow[g] = 0u;  // (a plan with runs whose policy chose a longer lead: a walker per chunk)
+    sc = chunks[act ? g : total - 1u];  // idle lanes shadow the last chunk and store nothing
+  }
   const FrameDev f = frames[sc.frame];
   const int lb = lut[f.qidx].lb8 + 1, cb = lut[f.qidx].cb8 + 1;  // DC + raw bytes of a luma / chroma block
   // first byte parsed: LEAD bytes before the chunk, or the packet's first byte where the packet does not reach that
@@ -233,7 +314,17 @@ __device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, con
   const uint32_t cstart = sc.c * (uint32_t)kSpecChunk;
   const uint32_t start = cstart > (uint32_t)LEAD ? cstart - (uint32_t)LEAD : 0u;
   const int take_tile = (int)((cstart - start) / (uint32_t)kSpecTile);  // the tile the walker's own chunk begins with
-  const int end_tile = take_tile + kSpecChunk / kSpecTile;             // ... and the first tile past it
+  const int end_tile = take_tile + kChunkTiles;                        // ... and the first tile past it
+  // tiles parsed: every lane of the launch the same number (a run shorter than S, or one that started at byte 0 without
+  // the whole lead, is through earlier and parses on for nothing, as a lone chunk's walker does today)
+  const int ntiles = RUNS ? LEAD / kSpecTile + (int)ra.S * kChunkTiles : kSpan / kSpecTile;
+  if constexpr (RUNS) {
+    for (uint32_t j = 0; j < nch; j++) {
+      rs.fixflag[chunk0 + j] = 0;
+      ra.brow[chunk0 + j] = g + 1u;
+      wstart[chunk0 + j] = start;
+    }
+  }
   const uint8_t* gp = stream + f.data_off + start;
   const uint32_t sh = (uint32_t)((uintptr_t)gp & 3u);
   const uint32_t* g4 = (const uint32_t*)(gp - sh);
@@ -242,11 +333,25 @@ __device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, con
 
   // ---- one tile = 32 dwords + the one after them (for the funnel shift), bytes past the packet read 0 ----
   uint32_t buf[33];
+  bool buf_past = false;  // the lane's tile in flight lies past its packet's end: it is to read as zeros (second form below)
   auto request = [&](int t) {
     const int d0 = t * (kSpecTile / 4);
-    if (__all(avail >= 4 * (d0 + 33))) {  // every lane's tile lies inside its packet
+    buf_past = false;
+    const int left = avail - 4 * d0;  // bytes of the packet from the tile's first dword on
+    if (__all(left >= 4 * 33)) {  // every lane's tile lies inside its packet
 #pragma unroll
       for (int k = 0; k < 33; k++) buf[k] = g4[d0 + k];
+    } else if (__all(left >= 4 * 33 || (left <= 0 && avail >= 4 * 33))) {
+      // Some lanes are PAST their packet's end — the walker of a packet's last chunk parses on to the end of its span,
+      // the walker of a run shorter than S to the end of the longest — and no lane's tile straddles the end: those
+      // lanes fetch their own first tile again (it lies inside the packet) and the tile is zeroed when it is taken out
+      // of `buf`.  No lane is masked, so the loads stay in flight while the tile before is parsed; the form below waits
+      // for each of its 33 loads in turn, which a launch of walkers per chunk hides behind its other waves and a launch
+      // of runs, where most waves hold such a lane, does not (profiles/spec_runs/why_3072.txt).
+      buf_past = left <= 0;
+      const uint32_t* const src = g4 + (buf_past ? 0 : d0);
+#pragma unroll
+      for (int k = 0; k < 33; k++) buf[k] = src[k];
     } else {
 #pragma unroll
       for (int k = 0; k < 33; k++) {
@@ -305,15 +410,33 @@ __device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, con
   uint32_t take = 0;  // where this walker's chunk takes over from its predecessor (chunk 0: byte 0, record 0)
   uint32_t tail = 0;  // where the next chunk has to take over: the last unit start below the end of this one
   uint32_t cnt_end = 0;  // block starts below the end of the walker's chunk
-  uint32_t* const out_bits = recbits + spec_bits_dword(gw, 0);
+  uint32_t* const out_bits = RUNS ? ra.runbits + spec_bits_dword_t(gw, 0, spec_run_tiles(ra.S)) : recbits + spec_bits_dword(gw, 0);
+  // RUNS: the hand-over pairs at the chunk boundaries of the run, tile take_tile + j * kChunkTiles for j = 0 .. nch:
+  // the end of chunk j - 1 and the start of chunk j, ONE value for both (what makes the boundary true by construction)
+  uint32_t* const hand32 = (uint32_t*)hand;
+  auto run_edge = [&](int t) {
+    const int rel = t - take_tile;
+    const bool edge = rel >= 0 && rel % kChunkTiles == 0 && rel / kChunkTiles <= (int)nch;
+    if (!__any(edge)) return;
+    const uint32_t v = last_aligned_below(t);
+    if (!edge) return;
+    const uint32_t j = (uint32_t)(rel / kChunkTiles);
+    if (j > 0u) {
+      hand32[2u * (chunk0 + j - 1u) + 1u] = v;  // .y: what the next chunk must take over from
+      nrec[chunk0 + j - 1u] = cnt;              // block starts the walker saw up to the end of that chunk
+    }
+    if (j < nch) hand32[2u * (chunk0 + j)] = sc.c + j ? v : 0u;  // .x (a packet's chunk 0: byte 0, record 0)
+  };
   uint4 tb = make_uint4(0, 0, 0, 0);  // the tile's start bits
 
   request(0);
-  for (int t = 0; t < kSpan / kSpecTile; t++) {
+  for (int t = 0; t < ntiles; t++) {
     // the tile is parsed out of registers (fully unrolled: 128 byte steps); staging it in LDS for a
     // smaller loop body capped the kernel at 11 waves per CU
     // the two hand-over points, per lane (walkers that started at byte 0 reach theirs earlier than the others)
-    if (__any(t == take_tile || t == end_tile)) {
+    if constexpr (RUNS) {
+      run_edge(t);
+    } else if (__any(t == take_tile || t == end_tile)) {
       const uint32_t v = last_aligned_below(t);
       if (t == take_tile) take = sc.c ? v : 0u;
       if (t == end_tile) {
@@ -322,12 +445,17 @@ __device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, con
       }
     }
     uint32_t cur[33];
+    if (__any(buf_past)) {
 #pragma unroll
-    for (int k = 0; k < 33; k++) cur[k] = buf[k];
+      for (int k = 0; k < 33; k++) cur[k] = buf_past ? 0u : buf[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 33; k++) cur[k] = buf[k];
+    }
     // the bits of the tile before leave now, BEFORE the next tile's loads are queued: loads and stores
     // complete in order, so a store queued after those loads would have to be waited for with them
     if (t > 0) *(uint4*)(out_bits + (size_t)(t - 1) * 256u) = tb;
-    if (t + 1 < kSpan / kSpecTile) request(t + 1);  // in flight while this tile is parsed
+    if (t + 1 < ntiles) request(t + 1);  // in flight while this tile is parsed
     // the first byte's token value and weight; every step computes them for the byte after it
     int tm_, wtm_;
     {
@@ -376,7 +504,11 @@ __device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, con
     cnt += (uint32_t)(__builtin_popcount(bw[0]) + __builtin_popcount(bw[1]) + __builtin_popcount(bw[2]) +
                       __builtin_popcount(bw[3]));
   }
-  *(uint4*)(out_bits + (size_t)(kSpan / kSpecTile - 1) * 256u) = tb;
+  *(uint4*)(out_bits + (size_t)(ntiles - 1) * 256u) = tb;
+  if constexpr (RUNS) {
+    run_edge(ntiles);  // (runs of S chunks with the whole lead end with the loop)
+    return;
+  }
   if (end_tile == kSpan / kSpecTile) {  // (walkers with the whole lead end with the loop)
     tail = last_aligned_below(kSpan / kSpecTile);
     cnt_end = cnt;
@@ -388,42 +520,48 @@ __device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, con
   }
 }
 
-// One form, named by the host (plans without a policy: MI_RTJ_SPEC = 1 / 3 / 4, tests).
-template <bool PHASE, int LEAD>
+// One form, named by the host (plans without a policy: MI_RTJ_SPEC = 1 / 3 / 4, tests).  RUNS: a lane per run of the
+// plan's run list (short lead only), else a lane per chunk.
+template <bool PHASE, int LEAD, bool RUNS = false>
 __global__ __launch_bounds__(64) void k_spec_walk(const FrameDev* __restrict__ frames,
                                                    const SpecChunkDev* __restrict__ chunks, uint32_t total,
                                                    const uint8_t* __restrict__ stream,
                                                    const QTab* __restrict__ lut, uint32_t* __restrict__ recbits,
                                                    uint32_t* __restrict__ nrec, uint32_t* __restrict__ wstart,
-                                                   uint2* __restrict__ hand, const SpecReset rs) {
+                                                   uint2* __restrict__ hand, const SpecReset rs, const SpecRunArgs ra) {
   __shared__ __attribute__((aligned(16))) uint8_t s_ring[64 * kSpecRingRow];
-  spec_walk_body<PHASE, LEAD>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs);
+  spec_walk_body<PHASE, LEAD, RUNS>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
 }
 
 // The form the plan's policy state names (none while the speculation is paused, k_spec_policy): ONE dispatch whatever
 // the lead.  (Round 3 first queued the three forms as three kernels of which two returned at once.)
-template <bool PHASE>
+// RUNS (a plan with runs, a kernel of its own so that the other plans' keeps its registers): the short lead walks runs;
+// the grid is sized for a walker per chunk, which the longer leads — noisy content — still are, and with the short lead
+// the waves past the last run leave at once.
+template <bool PHASE, bool RUNS = false>
 __global__ __launch_bounds__(64) void k_spec_walk_any(const FrameDev* __restrict__ frames,
                                                        const SpecChunkDev* __restrict__ chunks, uint32_t total,
                                                        const uint8_t* __restrict__ stream,
                                                        const QTab* __restrict__ lut, uint32_t* __restrict__ recbits,
                                                        uint32_t* __restrict__ nrec, uint32_t* __restrict__ wstart,
-                                                       uint2* __restrict__ hand, const SpecReset rs,
+                                                       uint2* __restrict__ hand, const SpecReset rs, const SpecRunArgs ra,
                                                        const uint32_t* __restrict__ state) {
   __shared__ __attribute__((aligned(16))) uint8_t s_ring[64 * kSpecRingRow];
   if (state[kSpecStPause]) return;
   const uint32_t level = state[kSpecStLong];  // wave-uniform
   if (level == 0u)
-    spec_walk_body<PHASE, kSpecLead>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs);
+    spec_walk_body<PHASE, kSpecLead, RUNS>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
   else if (level == 1u)
-    spec_walk_body<PHASE, kSpecLeadLong>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs);
+    spec_walk_body<PHASE, kSpecLeadLong>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
   else
-    spec_walk_body<PHASE, kSpecLeadVery>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs);
+    spec_walk_body<PHASE, kSpecLeadVery>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
 }
 
 // One workgroup per packet: the chain check, the block numbering, and — the numbering is all it needs —
 // the block-offset index itself.  A packet that fails goes on the exact kernels' to-do list (they then
 // rewrite its index).
+// RUNS: a plan with runs (a kernel of its own: the other plans' is the one it was).
+template <bool RUNS>
 __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev* __restrict__ frames,
                                                       const uint32_t* __restrict__ spec_base,
                                                       const QTab* __restrict__ lut,
@@ -433,7 +571,8 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
                                                       uint32_t* __restrict__ ntodo, const uint32_t* __restrict__ state,
                                                       const uint32_t* __restrict__ wstart,
                                                       const uint2* __restrict__ hand, uint2* __restrict__ fix,
-                                                      uint32_t* __restrict__ nfix, uint8_t* __restrict__ fixflag, int pass) {
+                                                      uint32_t* __restrict__ nfix, uint8_t* __restrict__ fixflag, int pass,
+                                                      const SpecRunArgs ra) {
   if (state && state[kSpecStPause]) {  // paused (k_spec_policy): nothing was walked, nothing is proven
     if (threadIdx.x == 0) ok[blockIdx.x] = 0;
     return;
@@ -449,6 +588,8 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
   // macroblock phase they assumed; the unit of the chain check is then the block, and the phase follows
   // from the global block number
   const uint32_t last = 6u * f.nmb;  // the index holds one entry past the last block: the end position
+  // (a plan with runs) this launch's walkers walked runs: the short lead — with a policy, the lead its state names
+  const bool run_walkers = RUNS && (!state || state[kSpecStLong] == 0u);
   uint32_t* const out = blkoff + f.blk_base;
   if (tid == 0) {
     s_carry[1] = 0;
@@ -477,6 +618,13 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
             soft = 1;
             fix[atomicAdd(nfix, 1u)] = make_uint2(sc0 + c + 1u, t);
             fixflag[sc0 + c + 1u] = 1;  // (k_spec_repair: walkers to repair that follow one another are one wave's job)
+            // A run walker that is out of step at its first chunk may be at its later ones, whose boundaries inside the
+            // run hold by construction and show nothing: they are marked as following (2, no list entry), so that the
+            // wave that walks the first chunk again looks at each of them, and at the run behind, in turn
+            if constexpr (RUNS) {
+              if (const uint32_t br = ra.brow[sc0 + c + 1u])
+                for (uint32_t k = 1; k < ra.runs[br - 1u].n; k++) fixflag[sc0 + c + 1u + k] = 2;
+            }
           } else {
             bad = 1;
           }
@@ -522,10 +670,29 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
         m[u] = have && base[u] <= last ? min(s_cnt[j], last + 1u - base[u]) : 0u;  // clipped to the packet's own index
         start[u] = wstart[sc0 + c0 + j];
         first[u] = s_i0[j];
-        const uint32_t R = sc0 + c0 + j;  // the walker whose starts are copied
+        const uint32_t R = sc0 + c0 + j;  // the chunk whose starts are copied
+        // A plan with runs: the chunk's bits are its run walker's (relative to the run's first byte, as wstart and the
+        // hand-over points of the chunk are), or its own row's once k_spec_repair has walked it again.  Of a run walker's
+        // bits only those below the end of the chunk are looked at: the ones behind belong to the run's next chunk.
+        // In the first pass nothing has been repaired yet: run and first byte follow from the chunk's number, and the
+        // bits are asked for together with the batch's other loads, not behind them.
+        uint32_t br = 0, first_byte = 0;
+        if constexpr (RUNS) {
+          if (pass == 1 && run_walkers) {
+            const uint32_t r = (c0 + j) / ra.S;
+            br = ra.rbase[blockIdx.x] + r + 1u;
+            first_byte = r ? r * ra.S * (uint32_t)kSpecChunk - (uint32_t)kSpecLead : 0u;
+          } else {
+            br = ra.brow[R];
+            first_byte = start[u];
+          }
+        }
+        const uint32_t* const bits = br ? ra.runbits : recbits;
+        const uint32_t wk = br ? br - 1u : R, tiles = br ? spec_run_tiles(ra.S) : (uint32_t)kSpecTilesMax;
+        const uint32_t kend = br ? min(tiles * 4u, ((c0 + j + 1u) * (uint32_t)kSpecChunk - first_byte + 31u) >> 5) : tiles * 4u;
 #ifdef MIRTJ_EXP_VER_FROM_ZERO  // A/B (short leads only): every bit of the span, ranks counted from the walker's first byte
-        w0[u] = m[u] ? recbits[spec_bits_dword(R, (uint32_t)lane)] : 0u;
-        w1[u] = m[u] ? recbits[spec_bits_dword(R, (uint32_t)lane + 64u)] : 0u;
+        w0[u] = m[u] ? bits[spec_bits_dword_t(wk, (uint32_t)lane, tiles)] : 0u;
+        w1[u] = m[u] ? bits[spec_bits_dword_t(wk, (uint32_t)lane + 64u, tiles)] : 0u;
         first[u] = c0 + j < nsc && c0 + j ? hand[sc0 + c0 + j].x >> 16 : 0u;
         continue;
 #endif
@@ -534,8 +701,8 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
         // kernel took 2.04 ms per 16,384 pictures instead of 1.60 (profiles/r03/ab_verify_bit_addressing.txt)
         const uint32_t kt = first[u] >> 5;  // the dword of the hand-over point
         const uint32_t k0 = (kt & ~3u) + (uint32_t)lane, k1 = k0 + 64u;
-        w0[u] = m[u] && k0 >= kt && k0 < (uint32_t)(kSpecTilesMax * 4) ? recbits[spec_bits_dword(R, k0)] : 0u;
-        w1[u] = m[u] && k1 < (uint32_t)(kSpecTilesMax * 4) ? recbits[spec_bits_dword(R, k1)] : 0u;
+        w0[u] = m[u] && k0 >= kt && k0 < kend ? bits[spec_bits_dword_t(wk, k0, tiles)] : 0u;
+        w1[u] = m[u] && k1 < kend ? bits[spec_bits_dword_t(wk, k1, tiles)] : 0u;
         if (k0 == kt) w0[u] &= 0xFFFFFFFFu >> (first[u] & 31u);  // starts before the hand-over point (bit 31 = first byte)
       }
 #pragma unroll
@@ -627,7 +794,7 @@ __global__ __launch_bounds__(64) void k_spec_repair(const FrameDev* __restrict__
                                                      uint2* __restrict__ hand, const uint2* __restrict__ fix,
                                                      uint32_t* __restrict__ nfix,
                                                      const uint8_t* __restrict__ fixflag, uint32_t total,
-                                                     const uint32_t* __restrict__ state) {
+                                                     const uint32_t* __restrict__ state, uint32_t* __restrict__ brow) {
   __shared__ uint32_t s_bits[kSpecTilesMax * 4];
   if (state && state[kSpecStPause]) return;  // paused: no walker ran, the list is the last unpaused launch's  // the re-walked span's start bits (at most kSpecSpan bytes)
   const uint32_t n = min(*nfix, total);  // (the count also takes the walkers repaired beyond the list: policy's figure)
@@ -640,7 +807,20 @@ __global__ __launch_bounds__(64) void k_spec_repair(const FrameDev* __restrict__
     const uint32_t frame = chunks[w].frame;
     const FrameDev f = frames[frame];
     bool listed = true;  // walker w is on the list (marked)
+    uint32_t mark = 1u;  // its mark: 1 = it has a list entry, 2 = a later chunk of a run whose first chunk has one (k_spec_verify)
     for (int guard = 0; guard < 4096; guard++) {
+      // (a plan with runs) a later chunk of a listed run whose walker had fallen into step by then takes over from the
+      // very byte this wave has arrived at: its records stay, and the wave goes on from where IT hands over — the chunks
+      // behind it are this wave's job all the same, their own waves have left
+      if (mark == 2u && wstart[w] + (hand[w].x & 0xFFFFu) == from) {
+        from = wstart[w] + (hand[w].y & 0xFFFFu);
+        if (w + 1u >= total || chunks[w + 1u].frame != frame) break;
+        mark = fixflag[w + 1u];
+        if (mark == 0u && wstart[w + 1u] + (hand[w + 1u].x & 0xFFFFu) == from) break;  // (as below)
+        listed = mark != 0u;
+        w++;
+        continue;
+      }
       const SpecChunkDev sc = chunks[w];
       const uint32_t limit = (sc.c + 1u) * (uint32_t)kSpecChunk;  // where the walker's span ends
       uint32_t take, tail;
@@ -655,12 +835,14 @@ __global__ __launch_bounds__(64) void k_spec_repair(const FrameDev* __restrict__
         nrec[w] = cnt;
         wstart[w] = from;
         hand[w] = make_uint2(take, tail);
+        if (brow) brow[w] = 0u;  // (a plan with runs) the chunk's bits are in its own row from now on
       }
-      if (!listed) extra++;
+      if (mark != 1u) extra++;
       from += tail & 0xFFFFu;  // the last (macro)block start below the end of this chunk: where the next walker takes over
       // wave-uniform from here: does the next walker of this packet need the same?
       if (w + 1u >= total || chunks[w + 1u].frame != frame) break;
-      const bool next_listed = fixflag[w + 1u] != 0;
+      mark = fixflag[w + 1u];
+      const bool next_listed = mark != 0u;
       if (next_listed && !listed) break;  // the first of another wave's run
       if (!next_listed && wstart[w + 1u] + (hand[w + 1u].x & 0xFFFFu) == from) break;  // it takes over where it should
       listed = next_listed;
