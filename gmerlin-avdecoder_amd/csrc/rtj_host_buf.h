@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "../../include/mi_rtjpeg.h"
+#include "host_owned.h"
 
 namespace {
 
@@ -21,34 +22,7 @@ int fail(mi_rtj_ctx* c, int code, const char* fmt, ...);
                   __FILE__, __LINE__);                                                        \
   } while (0)
 
-// `cap` elements at `p`, owned: move-only, freed by the destructor
-template <class T, hipError_t (*Free)(void*)>
-struct Owned {
-  T* p = nullptr;
-  uint64_t cap = 0;
-
-  Owned() = default;
-  Owned(const Owned&) = delete;
-  Owned& operator=(const Owned&) = delete;
-  Owned(Owned&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
-  Owned& operator=(Owned&& o) noexcept {
-    if (this != &o) {
-      release();
-      std::swap(p, o.p);
-      std::swap(cap, o.cap);
-    }
-    return *this;
-  }
-  ~Owned() { release(); }
-  operator T*() const { return p; }
-  void release() {
-    if (p) (void)Free(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-// Device memory.  It only ever grows.
+// Device memory (Owned: host_owned.h).  It only ever grows.
 template <class T>
 struct DevBuf : Owned<T, hipFree> {
   // Room for n elements (+ pad_bytes behind them).  Nothing happens if they fit.  Otherwise work queued on `stream` may

@@ -1,6 +1,7 @@
 """ctypes view of include/mi_dv.h (libmi_dv.so, the DV decoder and encoder: 525/60 4:1:1, 625/50 4:2:0 and 625/50 4:1:1 at
 25 Mbit/s, both line systems in 4:2:2 at 50 Mbit/s).  No CPU path: without the library or a gfx950 device construction raises MiDvError with
 the library's own message."""
+import contextlib
 import ctypes as C
 import os
 
@@ -199,6 +200,37 @@ class MiDv:
     def sync(self):
         self._chk(self.L.mi_dv_sync(self.c))
 
+    def _times(self, fn):
+        ms, n = C.c_float(), C.c_int()
+        self._chk(fn(self.c, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    @contextlib.contextmanager
+    def _resident(self, *what):
+        """device buffers for the length of a with block: an array is uploaded, an int is a size in bytes, None stays None"""
+        ds = []
+        try:
+            for a in what:
+                ds.append(None if a is None else self.alloc(a if isinstance(a, int) else a.nbytes))
+                if isinstance(a, np.ndarray):
+                    self.h2d(ds[-1], a)
+            yield ds
+        finally:
+            for d in ds:
+                if d:
+                    self.free(d)
+
+    @staticmethod
+    def _planes(system, strides, planes=None):
+        """(planes, their pointers, strides) as the one-frame calls take them; planes None: zeros of the system's picture,
+        strides None: the system's plane widths"""
+        planes_wh = geometry(system)[2]
+        if strides is None:
+            strides = tuple(w for w, _ in planes_wh)
+        if planes is None:
+            planes = [np.zeros(strides[i] * planes_wh[i][1], np.uint8) for i in range(3)]
+        return planes, (u8p * 3)(*[p.ctypes.data_as(u8p) for p in planes]), (C.c_int * 3)(*strides)
+
     def decode_batch(self, d_frames, n, d_pics):
         self._chk(self.L.mi_dv_decode_batch(self.c, d_frames, n, d_pics))
 
@@ -207,9 +239,7 @@ class MiDv:
 
     def kernel_times(self):
         """(total milliseconds, launches) of k_dv_decode since the last call"""
-        ms, n = C.c_float(), C.c_int()
-        self._chk(self.L.mi_dv_kernel_times(self.c, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return self._times(self.L.mi_dv_kernel_times)
 
     def decode_frames(self, frames, system=SYS_525_60):
         """host frames (n x the system's frame bytes, uint8) -> host pictures (n x its picture bytes), through the batch
@@ -217,28 +247,18 @@ class MiDv:
         fb, pb, _ = geometry(system)
         frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, fb)
         n = frames.shape[0]
-        df, dp = self.alloc(n * fb), self.alloc(n * pb)
-        try:
-            self.h2d(df, frames)
+        with self._resident(frames, n * pb) as (df, dp):
             if system == SYS_525_60:
                 self.decode_batch(df, n, dp)
             else:
                 self.decode_batch_sys(system, df, n, dp)
             self.sync()
             return self.d2h(dp, n * pb).reshape(n, pb)
-        finally:
-            self.free(df)
-            self.free(dp)
 
     def decode_frame(self, frame, strides=None, system=SYS_525_60):
         """one host frame into three planes of the given strides (default: the system's plane widths)"""
-        _, _, planes_wh = geometry(system)
-        if strides is None:
-            strides = tuple(w for w, _ in planes_wh)
         frame = np.ascontiguousarray(frame, np.uint8)
-        planes = [np.zeros(strides[i] * planes_wh[i][1], np.uint8) for i in range(3)]
-        pp = (u8p * 3)(*[p.ctypes.data_as(u8p) for p in planes])
-        st = (C.c_int * 3)(*strides)
+        planes, pp, st = self._planes(system, strides)
         if system == SYS_525_60:
             self._chk(self.L.mi_dv_decode_frame(self.c, frame.ctypes.data_as(u8p), frame.nbytes, pp, st))
         else:
@@ -260,31 +280,16 @@ class MiDv:
         n = frames.shape[0]
         if prev is not None:
             prev = np.ascontiguousarray(prev, np.uint8).reshape(len(runs) if runs else 1, pb)
-        df, dp = self.alloc(n * fb), self.alloc(n * pb)
-        dq = self.alloc(prev.nbytes) if prev is not None else None
-        try:
-            self.h2d(df, frames)
-            if prev is not None:
-                self.h2d(dq, prev)
+        with self._resident(frames, n * pb, prev) as (df, dp, dq):
             self.decode_batch_held(system, df, n, dp, runs, dq, sta_mask)
             self.sync()
             return self.d2h(dp, n * pb).reshape(n, pb)
-        finally:
-            self.free(df)
-            self.free(dp)
-            if dq:
-                self.free(dq)
 
     def decode_frame_held(self, frame, system, strides=None, sta_mask=0):
         """decode_frame with held macroblocks from the picture of the frame this call decoded last (none: the first frame,
         after hold_reset, after a frame of another system or a refused one) -> (planes, macroblocks taken from it)"""
-        _, _, planes_wh = geometry(system)
-        if strides is None:
-            strides = tuple(w for w, _ in planes_wh)
         frame = np.ascontiguousarray(frame, np.uint8)
-        planes = [np.zeros(strides[i] * planes_wh[i][1], np.uint8) for i in range(3)]
-        pp = (u8p * 3)(*[p.ctypes.data_as(u8p) for p in planes])
-        st = (C.c_int * 3)(*strides)
+        planes, pp, st = self._planes(system, strides)
         held = C.c_int()
         self._chk(self.L.mi_dv_decode_frame_held(self.c, system, frame.ctypes.data_as(u8p), frame.nbytes, pp, st, sta_mask,
                                                  C.byref(held)))
@@ -301,9 +306,7 @@ class MiDv:
 
     def hold_times(self):
         """(total milliseconds, launches) of the hold pass since the last call; kernel_times keeps k_dv_decode's"""
-        ms, n = C.c_float(), C.c_int()
-        self._chk(self.L.mi_dv_hold_times(self.c, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return self._times(self.L.mi_dv_hold_times)
 
     # ---- the encoder (include/mi_dv.h; parity unpinned like the decoder) ----
     def encode_batch(self, system, d_pics, n, d_frames, flags=3):
@@ -316,35 +319,24 @@ class MiDv:
         fb, pb, _ = geometry(system)
         pics = np.ascontiguousarray(pics, np.uint8).reshape(-1, pb)
         n = pics.shape[0]
-        dp, df = self.alloc(n * pb), self.alloc(n * fb)
-        try:
-            self.h2d(dp, pics)
+        with self._resident(pics, n * fb) as (dp, df):
             self.encode_batch(system, dp, n, df, flags)
             self.sync()
             return self.d2h(df, n * fb).reshape(n, fb)
-        finally:
-            self.free(dp)
-            self.free(df)
 
     def encode_frame(self, planes, system, strides=None, flags=3, cap=None):
         """one picture from three host planes of the given strides (default: the system's plane widths) -> one host frame;
         cap: the room offered for it (default: the system's frame bytes)"""
-        fb, _, planes_wh = geometry(system)
-        if strides is None:
-            strides = tuple(w for w, _ in planes_wh)
-        planes = [np.ascontiguousarray(p, np.uint8) for p in planes]
+        fb = geometry(system)[0]
+        planes, pp, st = self._planes(system, strides, [np.ascontiguousarray(p, np.uint8) for p in planes])
         cap = fb if cap is None else cap
         frame = np.zeros(max(cap, 1), np.uint8)
-        pp = (u8p * 3)(*[p.ctypes.data_as(u8p) for p in planes])
-        st = (C.c_int * 3)(*strides)
         self._chk(self.L.mi_dv_encode_frame(self.c, system, pp, st, frame.ctypes.data_as(u8p), cap, flags))
         return frame[:fb]
 
     def encode_times(self):
         """(total milliseconds, launches) of k_dv_encode since the last call; kernel_times keeps k_dv_decode's"""
-        ms, n = C.c_float(), C.c_int()
-        self._chk(self.L.mi_dv_encode_times(self.c, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return self._times(self.L.mi_dv_encode_times)
 
     def encode_stats(self):
         """(segments per chosen quantisation number [16], levels the overflow rule dropped) of the last encoded batch"""

@@ -75,7 +75,9 @@ int mi_dv_sync(mi_dv_ctx *c);
  * below read what a stream says about its own damage). */
 int mi_dv_decode_batch(mi_dv_ctx *c, const void *d_frames, int n, void *d_pics);
 /* Device time of k_dv_decode: every mi_dv_decode_batch brackets its launch with HIP events on the instance's stream;
- * this sums them over the launches since the last call (synchronises, then forgets them). */
+ * this sums them over the launches since the last call (synchronises, then forgets them).  Where nobody asks, the newest
+ * 4096 launches are kept and older ones forgotten; so do mi_dv_hold_times and mi_dv_encode_times, each with 4096 of its
+ * own. */
 int mi_dv_kernel_times(mi_dv_ctx *c, float *total_ms, int *launches);
 
 /* One frame from host memory into the caller's planes (Y, Cb, Cr) with the caller's strides — what a
