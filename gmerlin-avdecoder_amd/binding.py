@@ -34,7 +34,7 @@ EXPORTS = ["mi_rtj_device_count", "mi_rtj_create", "mi_rtj_destroy", "mi_rtj_las
            "mi_rtj_pipe_pending", "mi_rtj_pipe_submit", "mi_rtj_pipe_next", "mi_rtj_pipe_peek_tag", "mi_rtj_pipe_flush",
            "mi_rtj_pipe_profile", "mi_rtj_pipe_times", "mi_rtj_plan_set_runs", "mi_rtj_plan_run_times",
            "mi_rtj_plan_run_stats", "mi_rtj_set_format", "mi_rtj_get_format", "mi_rtj_yuv422_to_rgb24",
-           "mi_rtj_encode_bound_fmt", "mi_rtj_encode_frames_fmt", "mi_rtj_encode_stream_fmt"]
+           "mi_rtj_encode_bound_fmt", "mi_rtj_encode_frames_fmt", "mi_rtj_encode_stream_fmt", "mi_rtj_plan_set_runs_fmt"]
 
 # picture formats (mi_rtj_set_format): RTJ_YUV420 / RTJ_YUV422 / RTJ_RGB8 of the reference
 FMT_YUV420, FMT_YUV422, FMT_GREY = 0, 1, 2
@@ -95,6 +95,7 @@ def load():
     L.mi_rtj_plan_overlapped.argtypes = [vp]
     L.mi_rtj_plan_step_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.mi_rtj_plan_set_runs.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.mi_rtj_plan_set_runs_fmt.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.mi_rtj_plan_run_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     L.mi_rtj_plan_run_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.mi_rtj_pipe_create.argtypes = [vp, C.c_int, C.c_int, C.c_int]
@@ -219,6 +220,13 @@ class Plan:
         lengths = [int(x) for x in (lengths or [])]
         arr = (C.c_int * max(len(lengths), 1))(*lengths)
         self.owner._chk(self.owner.L.mi_rtj_plan_set_runs(self.h, len(lengths), arr))
+
+    def set_runs_fmt(self, lengths):
+        """set_runs for a plan of any format (mi_rtj_plan_set_runs_fmt): on a 4:2:0 plan it is set_runs; on a 4:2:2 or
+        greyscale plan "block b" of the run rule is in the format's stream order.  Same errors, same queries."""
+        lengths = [int(x) for x in (lengths or [])]
+        arr = (C.c_int * max(len(lengths), 1))(*lengths)
+        self.owner._chk(self.owner.L.mi_rtj_plan_set_runs_fmt(self.h, len(lengths), arr))
 
     def run_times(self):
         """(ms of the run kernels summed over the decodes since profile(True), decodes that ran them)."""

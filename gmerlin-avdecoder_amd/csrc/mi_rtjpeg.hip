@@ -185,8 +185,8 @@ struct Overlap {
   }
 };
 
-// Runs (mi_rtj_plan_set_runs, rtj_runs_kernels.h): phase 2 resolves the unchanged blocks of pictures k > 0 of a run
-// behind the transform.  Everything is made by set_runs; a launch only queues the three kernels.
+// Runs (mi_rtj_plan_set_runs / _fmt, rtj_runs_kernels.h): phase 2 resolves the unchanged blocks of pictures k > 0 of a
+// run behind the transform.  Everything is made by set_runs; a launch only queues the three kernels of the plan's format.
 struct Runs {
   int n_runs = 0;                    // runs as set (0: independent pictures)
   uint32_t list = 0, chunks = 0;     // runs of two or more pictures / their chunks: what phase 2 covers
@@ -450,14 +450,31 @@ enum { kLaunchIndex = 1, kLaunchDecode = 2, kLaunchAll = 3 };
 
 namespace {
 
+// phase 2's grids from the format's block and tile counts (rtj_runs_kernels.h): a lane per block of the largest picture
+// for the scans, a workgroup per tile of units (4:2:0 and 4:2:2: 32 macroblocks, greyscale: 64 blocks) for the copy
+RunGrids run_grids(const mi_rtj_plan* p) {
+  const Runs& r = p->runs;
+  const uint32_t tile = p->fmt == MI_RTJ_FMT_YUV422 ? RunTile<kFmtYUV422>::kUnits
+                        : p->fmt == MI_RTJ_FMT_GREY ? RunTile<kFmtGrey>::kUnits
+                                                    : (uint32_t)kRunTileMb;
+  const unsigned bx = (unsigned)(((uint64_t)kFormats[p->fmt].blk_per_mb * r.nmb_max + kRunScanThreads - 1) / kRunScanThreads);
+  RunGrids rg;
+  rg.items = r.chunks * (uint32_t)kRunSubs;
+  rg.mask = dim3(bx, std::min(r.chunks, kRunMaxGridY));
+  rg.carry = dim3(bx, std::min(r.list, kRunMaxGridY));
+  rg.copy = dim3((r.nmb_max + tile - 1) / tile, std::min(rg.items, kRunMaxGridY));
+  return rg;
+}
+
 // The stages are rtj_host_stages.h's, called in order; everything that sizes a grid is here.
 int plan_launch(mi_rtj_plan* p, const void* d_stream, void* d_out, int what = kLaunchAll, uint32_t dframe = 0,
                 int dcount = -1) {
   mi_rtj_ctx* c = p->ctx;
   Launch L(p, (const uint8_t*)d_stream);
-  if (p->fmt != MI_RTJ_FMT_YUV420)  // the serial index, a wave per packet, then the transform
+  if (p->fmt != MI_RTJ_FMT_YUV420)  // the serial index, a wave per packet, then the transform, then phase 2 of runs
     return launch_fmt(L, dim3(std::min<unsigned>((unsigned)p->n, 16384u)),
-                      dim3(kFormats[p->fmt].parts * p->max_groups, (unsigned)p->n), (uint8_t*)d_out);
+                      dim3(kFormats[p->fmt].parts * p->max_groups, (unsigned)p->n), p->runs.chunks > 0, run_grids(p),
+                      (uint8_t*)d_out);
   int rc;
   if ((rc = launch_open(L, what)) != MI_RTJ_OK) return rc;
   if (what & kLaunchIndex) {
@@ -512,13 +529,7 @@ int plan_launch(mi_rtj_plan* p, const void* d_stream, void* d_out, int what = kL
   }
   if (rc != MI_RTJ_OK) return rc;
   const bool runs = what == kLaunchAll && p->runs.chunks > 0;
-  RunGrids rg;
-  const unsigned bx = (unsigned)((6ull * p->runs.nmb_max + kRunScanThreads - 1) / kRunScanThreads);
-  rg.items = p->runs.chunks * (uint32_t)kRunSubs;
-  rg.mask = dim3(bx, std::min(p->runs.chunks, kRunMaxGridY));
-  rg.carry = dim3(bx, std::min(p->runs.list, kRunMaxGridY));
-  rg.copy = dim3((p->runs.nmb_max + kRunTileMb - 1) / kRunTileMb, std::min(rg.items, kRunMaxGridY));
-  if ((rc = stage_runs(L, runs, rg, (uint8_t*)d_out)) != MI_RTJ_OK) return rc;
+  if ((rc = stage_runs(L, runs, run_grids(p), (uint8_t*)d_out)) != MI_RTJ_OK) return rc;
   return launch_close(L, what, runs);
 }
 
@@ -901,20 +912,19 @@ int mi_rtj_plan_read_index(mi_rtj_plan* p, uint32_t* dst, size_t max_entries) {
   return MI_RTJ_OK;
 }
 
-int mi_rtj_plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len) {
-  if (!p) return MI_RTJ_ERR_ARG;
+// mi_rtj_plan_set_runs and mi_rtj_plan_set_runs_fmt behind their argument checks; `who` names the entry point in messages.
+// The rows of the mask and carry arrays and the extent of an output picture are the plan's format's.
+static int plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len, const char* who) {
   mi_rtj_ctx* c = p->ctx;
-  if (n_runs < 0 || (n_runs > 0 && !run_len)) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: bad argument");
-  if (p->fmt != MI_RTJ_FMT_YUV420)
-    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: runs are for 4:2:0 plans; this plan's format is %s",
-                kFormats[p->fmt].name);
+  const Format& F = kFormats[p->fmt];
+  if (n_runs < 0 || (n_runs > 0 && !run_len)) return fail(c, MI_RTJ_ERR_ARG, "%s: bad argument", who);
   // ---- check everything before anything changes: a refused call leaves the plan as it was ----
   std::vector<RunDev> runs;
   std::vector<RunChunkDev> chunks;
   uint64_t rows = 0, sum = 0;
   uint32_t nmb_max = 0;
   for (int r = 0; r < n_runs; r++) {
-    if (run_len[r] <= 0) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: run %d has length %d", r, run_len[r]);
+    if (run_len[r] <= 0) return fail(c, MI_RTJ_ERR_ARG, "%s: run %d has length %d", who, r, run_len[r]);
     sum += (uint64_t)run_len[r];
     if (sum > (uint64_t)p->n) break;
     const uint32_t f0 = (uint32_t)(sum - run_len[r]), len = (uint32_t)run_len[r];
@@ -923,14 +933,14 @@ int mi_rtj_plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len) {
     for (uint32_t k = 0; k < len; k++) {
       const FrameDev& f = p->h_frames[f0 + k];
       if (f.w != a.w || f.h != a.h)
-        return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: packet %u of run %d is %ux%u, the run's picture 0 is %ux%u "
-                    "(a size change inside a run is refused)", f0 + k, r, f.w, f.h, a.w, a.h);
-      span.emplace_back(f.out_off, f.out_off + (uint64_t)f.w * f.h * 3 / 2);
+        return fail(c, MI_RTJ_ERR_ARG, "%s: packet %u of run %d is %ux%u, the run's picture 0 is %ux%u "
+                    "(a size change inside a run is refused)", who, f0 + k, r, f.w, f.h, a.w, a.h);
+      span.emplace_back(f.out_off, f.out_off + (uint64_t)F.picture_bytes(f.w, f.h));
     }
     std::sort(span.begin(), span.end());
     for (size_t k = 1; k < span.size(); k++)
       if (span[k].first < span[k - 1].second)
-        return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: output pictures of run %d overlap", r);
+        return fail(c, MI_RTJ_ERR_ARG, "%s: output pictures of run %d overlap", who, r);
     if (len < 2) continue;  // picture 0 alone: nothing to resolve
     RunDev rd{};
     rd.chunk0 = (uint32_t)chunks.size();
@@ -942,7 +952,7 @@ int mi_rtj_plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len) {
       ch.count = std::min<uint32_t>(kRunChunk, len - j);
       ch.nmb = a.nmb;
       ch.row = rows;
-      rows += 6ull * a.nmb;
+      rows += (uint64_t)F.blk_per_mb * a.nmb;
       chunks.push_back(ch);
     }
     rd.nchunks = (uint32_t)chunks.size() - rd.chunk0;
@@ -950,10 +960,10 @@ int mi_rtj_plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len) {
     nmb_max = std::max(nmb_max, a.nmb);
   }
   if (n_runs > 0 && sum != (uint64_t)p->n)
-    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: run lengths add up to %llu, the plan has %d packets",
+    return fail(c, MI_RTJ_ERR_ARG, "%s: run lengths add up to %llu, the plan has %d packets", who,
                 (unsigned long long)sum, p->n);
   if ((uint64_t)chunks.size() * kRunSubs > 0xFFFFFFFFull)
-    return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: too many chunks");
+    return fail(c, MI_RTJ_ERR_ARG, "%s: too many chunks", who);
   // ---- make the new state, then swap it in (launches queued before keep using the old one until they are done) ----
   HIPCHK(c, hipSetDevice(c->device));
   Runs q;
@@ -972,7 +982,7 @@ int mi_rtj_plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len) {
     if (ok && e == hipSuccess) e = hipStreamSynchronize(s);  // (the host vectors go out of scope)
     if (!ok || e != hipSuccess) {
       (void)hipGetLastError();
-      return fail(c, MI_RTJ_ERR_NOMEM, "mi_rtj_plan_set_runs: %s (%llu chunk rows of %d runs)",
+      return fail(c, MI_RTJ_ERR_NOMEM, "%s: %s (%llu chunk rows of %d runs)", who,
                   ok ? hipGetErrorString(e) : "out of device memory", (unsigned long long)chunks.size(), (int)runs.size());
     }
   }
@@ -980,6 +990,20 @@ int mi_rtj_plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len) {
   p->runs = std::move(q);
   p->runs_ran = false;
   return MI_RTJ_OK;
+}
+
+int mi_rtj_plan_set_runs(mi_rtj_plan* p, int n_runs, const int* run_len) {
+  if (!p) return MI_RTJ_ERR_ARG;
+  if (n_runs < 0 || (n_runs > 0 && !run_len)) return fail(p->ctx, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: bad argument");
+  if (p->fmt != MI_RTJ_FMT_YUV420)
+    return fail(p->ctx, MI_RTJ_ERR_ARG, "mi_rtj_plan_set_runs: runs are for 4:2:0 plans; this plan's format is %s",
+                kFormats[p->fmt].name);  // (mi_rtj_plan_set_runs_fmt takes plans of every format)
+  return plan_set_runs(p, n_runs, run_len, "mi_rtj_plan_set_runs");
+}
+
+int mi_rtj_plan_set_runs_fmt(mi_rtj_plan* p, int n_runs, const int* run_len) {
+  if (!p) return MI_RTJ_ERR_ARG;
+  return plan_set_runs(p, n_runs, run_len, "mi_rtj_plan_set_runs_fmt");
 }
 
 int mi_rtj_plan_run_times(mi_rtj_plan* p, float* ms, int* launches) {

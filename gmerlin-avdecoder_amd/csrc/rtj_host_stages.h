@@ -117,18 +117,28 @@ void launch_spec_walk(bool two_types, int spec_mode, uint32_t* state, dim3 grid,
 }
 #undef WALK
 
-// ---- a 4:2:2 or greyscale plan: two kernels back to back on the instance's stream (rtj_format_kernels.h) — the serial
-// index, a wave per packet (MI_RTJ_K_EMIT), then the transform (MI_RTJ_K_DECODE).  No speculative or chunk-parallel
-// index, no second stream, no runs.
-int launch_fmt(Launch& L, dim3 igrid, dim3 dgrid, uint8_t* out) {
+struct RunGrids {
+  dim3 mask, carry, copy;
+  uint32_t items;
+};
+int stage_runs(Launch& L, bool runs, const RunGrids& g, uint8_t* out);
+
+// ---- a 4:2:2 or greyscale plan: kernels back to back on the instance's stream (rtj_format_kernels.h) — the serial
+// index, a wave per packet (MI_RTJ_K_EMIT), then the transform (MI_RTJ_K_DECODE), then phase 2 of a plan with runs
+// (mi_rtj_plan_set_runs_fmt), which reads the index this launch wrote.  No speculative or chunk-parallel index, no
+// second stream.
+int launch_fmt(Launch& L, dim3 igrid, dim3 dgrid, bool runs, const RunGrids& rg, uint8_t* out) {
   mi_rtj_plan* p = L.p;
   L.c->input_dirty = false;  // (everything runs on the instance's stream)
+  L.blk = p->blkoff;
   STAGE_CHK(L.clk.begin());
-  launch_index_fmt(p->fmt, igrid, L.ds, p->d_frames, (uint32_t)p->n, L.st, L.c->d_lut, p->blkoff);
+  launch_index_fmt(p->fmt, igrid, L.ds, p->d_frames, (uint32_t)p->n, L.st, L.c->d_lut, L.blk);
   STAGE_CHK(L.clk.end(MI_RTJ_K_EMIT));
   STAGE_CHK(L.clk.begin());
-  launch_decode_fmt(p->fmt, dgrid, L.ds, p->d_frames, L.st, L.c->d_lut, p->blkoff, out);
+  launch_decode_fmt(p->fmt, dgrid, L.ds, p->d_frames, L.st, L.c->d_lut, L.blk, out);
   STAGE_CHK(L.clk.end(MI_RTJ_K_DECODE));
+  STAGE_CHK(stage_runs(L, runs, rg, out));
+  p->runs_ran = runs;
   HIPCHK(L.c, hipGetLastError());
   p->ov.last = 0;
   p->launches++;
@@ -346,10 +356,7 @@ int stage_transform_classic(Launch& L, const Transform& T, bool all_parts) {
 }
 
 // ---- stage 6: phase 2 of a plan with runs: unchanged blocks from the run's earlier pictures, read from this launch's index ----
-struct RunGrids {
-  dim3 mask, carry, copy;
-  uint32_t items;
-};
+// (the three kernels of the plan's format; one set of books: run_ev, and launch_close / launch_fmt note runs_ran)
 int stage_runs(Launch& L, bool runs, const RunGrids& g, uint8_t* out) {
   mi_rtj_plan* p = L.p;
   const Runs& r = p->runs;
@@ -361,9 +368,19 @@ int stage_runs(Launch& L, bool runs, const RunGrids& g, uint8_t* out) {
     p->run_ev.push_back(rt);
   }
   if (!runs) return MI_RTJ_OK;
-  hipLaunchKernelGGL(k_runs_mask, g.mask, dim3(kRunScanThreads), 0, L.ds, p->d_frames, r.d_chunks, r.chunks, (const uint32_t*)L.blk, r.d_mask);
-  hipLaunchKernelGGL(k_runs_carry, g.carry, dim3(kRunScanThreads), 0, L.ds, r.d_runs, r.list, r.d_chunks, r.d_mask, r.d_carry, r.d_copied);
-  hipLaunchKernelGGL(k_runs_copy, g.copy, dim3(kRunCopyThreads), 0, L.ds, p->d_frames, r.d_chunks, g.items, r.d_mask, r.d_carry, out, r.d_copied);
+  if (p->fmt == MI_RTJ_FMT_YUV422) {
+    hipLaunchKernelGGL(k_runs_mask_fmt<kFmtYUV422>, g.mask, dim3(kRunScanThreads), 0, L.ds, p->d_frames, r.d_chunks, r.chunks, (const uint32_t*)L.blk, r.d_mask);
+    hipLaunchKernelGGL(k_runs_carry_fmt<kFmtYUV422>, g.carry, dim3(kRunScanThreads), 0, L.ds, r.d_runs, r.list, r.d_chunks, r.d_mask, r.d_carry, r.d_copied);
+    hipLaunchKernelGGL(k_runs_copy_fmt<kFmtYUV422>, g.copy, dim3(RunTile<kFmtYUV422>::kThreads), 0, L.ds, p->d_frames, r.d_chunks, g.items, r.d_mask, r.d_carry, out, r.d_copied);
+  } else if (p->fmt == MI_RTJ_FMT_GREY) {
+    hipLaunchKernelGGL(k_runs_mask_fmt<kFmtGrey>, g.mask, dim3(kRunScanThreads), 0, L.ds, p->d_frames, r.d_chunks, r.chunks, (const uint32_t*)L.blk, r.d_mask);
+    hipLaunchKernelGGL(k_runs_carry_fmt<kFmtGrey>, g.carry, dim3(kRunScanThreads), 0, L.ds, r.d_runs, r.list, r.d_chunks, r.d_mask, r.d_carry, r.d_copied);
+    hipLaunchKernelGGL(k_runs_copy_fmt<kFmtGrey>, g.copy, dim3(RunTile<kFmtGrey>::kThreads), 0, L.ds, p->d_frames, r.d_chunks, g.items, r.d_mask, r.d_carry, out, r.d_copied);
+  } else {
+    hipLaunchKernelGGL(k_runs_mask, g.mask, dim3(kRunScanThreads), 0, L.ds, p->d_frames, r.d_chunks, r.chunks, (const uint32_t*)L.blk, r.d_mask);
+    hipLaunchKernelGGL(k_runs_carry, g.carry, dim3(kRunScanThreads), 0, L.ds, r.d_runs, r.list, r.d_chunks, r.d_mask, r.d_carry, r.d_copied);
+    hipLaunchKernelGGL(k_runs_copy, g.copy, dim3(kRunCopyThreads), 0, L.ds, p->d_frames, r.d_chunks, g.items, r.d_mask, r.d_carry, out, r.d_copied);
+  }
   if (p->profile) HIPCHK(L.c, hipEventRecord(p->run_ev.back().b, L.ds));
   return MI_RTJ_OK;
 }

@@ -230,8 +230,15 @@ int mi_rtj_plan_overlapped(const mi_rtj_plan *plan);
  * inside a run is refused), or the output pictures of a run overlap one another.  Every buffer the runs need (about
  * 10 bytes per block and 64 pictures of a run: 125 MB for 16,384 pictures of 1080p) is allocated here; launches allocate
  * and synchronise nothing.  Synchronises the instance's stream.
- * Runs are 4:2:0 only: on a 4:2:2 or greyscale plan the call returns MI_RTJ_ERR_ARG and leaves the plan as it was. */
+ * This call takes 4:2:0 plans: on a 4:2:2 or greyscale plan it returns MI_RTJ_ERR_ARG and leaves the plan as it was;
+ * mi_rtj_plan_set_runs_fmt below takes plans of all three formats. */
 int mi_rtj_plan_set_runs(mi_rtj_plan *plan, int n_runs, const int *run_len);
+/* Runs on a plan of any format (the output of mi_rtj_encode_stream_fmt decoded in one launch).  On a 4:2:0 plan it is
+ * mi_rtj_plan_set_runs: the same kernels and buffers.  On a 4:2:2 or greyscale plan the semantics, the refusals and the
+ * queries below are the same, "block b" is in the format's stream order (4:2:2: Y, Y, Cb, Cr per 16 x 8 macroblock,
+ * lib/RTjpeg.c:2639-2686; greyscale: raster order, :2751-2772), and the three run kernels are the format's forms
+ * (k_runs_*_fmt, rtj_runs_kernels.h), queued behind the transform on the instance's stream. */
+int mi_rtj_plan_set_runs_fmt(mi_rtj_plan *plan, int n_runs, const int *run_len);
 /* While profiling (mi_rtj_plan_profile): device time of the run kernels summed over the decodes since profiling was
  * switched on, *launches = decodes that ran them.  (mi_rtj_plan_times keeps its kernels; mi_rtj_plan_step_times ends
  * a decode with runs at the end of its last run kernel.)  Synchronises the instance's stream. */
