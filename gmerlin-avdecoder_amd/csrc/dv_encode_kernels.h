@@ -12,9 +12,10 @@
 //                  Workgroups behind the video ones write the non-video DIF blocks of one sequence each (ids with the
 //                  channel bit, DSF, APT, VAUX stype, zeros elsewhere), so that one launch makes complete frames.
 //
-// Integer only; every multiplication's operands stay below 2^23 and its product below 2^31 (tests/dvenc.py asserts the
-// latter on what it encodes), so the 24-bit multiplier is exact.  Lane masks are 64 bits wide, and every loop carries a
-// bound no picture can reach.
+// Integer only; every multiplication's operands stay within 17 bits and its product within 29 (measured on the edge
+// pictures of tests/dvenc_edges.py, whose 0 / 255 sign patterns drive every coefficient as far as pixels can; the 24-bit
+// multiplier needs them below 2^23 and 2^31, which tests/test_dv_encode_edges_cpu.py asserts), so the 24-bit multiplier is
+// exact.  Lane masks are 64 bits wide, and every loop carries a bound no picture can reach.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -25,6 +25,11 @@ The encoder's own choices:
               144 class 2, else 3 (the float statement's thresholds on the same quantity); without the bit class 0.
   rate        the largest qno 0..15 at which the segment's 30 blocks need at most 2,680 bits; if 0 does not fit, the block
               with the most bits (the first such) loses its last non-zero level until it fits.
+
+Four of these rules are module-level callables (mode_rule, clip_level, fits, most_bits) and two are tables (CLASS_LIMITS,
+QUANT_SHIFT), so that a test can swap one and see which pictures notice; _mul is looked up by name at every call, so a test
+can record its operands.  The pictures built to reach every branch of the rules — named edge segments scattered over the
+segments of any system — are tests/dvenc_edges.py.
 """
 import numpy as np
 
@@ -72,10 +77,11 @@ VLC_AMP = (1, 2, 0, 1, 3, 4, 1, 2, 5, 6, 1, 1, 7, 8, 1, 1, 2, 3, 4, 9, 10, 11, 1
            2, 2, 2, 2, 3, 3, 5, 7, 7, 8, 9, 10, 11, 15, 16, 17)
 
 
-def _words():
+def _words(amps=256):
     """PAIR_VAL / PAIR_LEN [run 0..62][amplitude 0..255] of a (run, amplitude) pair without its sign, as put_pair spells it:
     the listed word; else the zeros on their own (listed up to run 5, else 1111110 rrrrrr) and then the amplitude with run 0
-    (listed up to 22, else 1111111 aaaaaaaa).  Amplitude 0 is unused.  And the end of block."""
+    (listed up to 22, else 1111111 aaaaaaaa).  Amplitude 0 is unused.  And the end of block.  amps: a test that removes the
+    clip asks for 512, and an amplitude above 255 then runs into the 1111111 in front of it."""
     listed, code, prev, eob = {}, 0, VLC_LEN[0], None
     for ln, run, amp in zip(VLC_LEN, VLC_RUN, VLC_AMP):
         code <<= ln - prev
@@ -85,9 +91,9 @@ def _words():
         else:
             listed.setdefault((run, amp), (code, ln))
         code += 1
-    val, length = np.zeros((63, 256), np.int64), np.zeros((63, 256), np.int64)
+    val, length = np.zeros((63, amps), np.int64), np.zeros((63, amps), np.int64)
     for run in range(63):
-        for amp in range(1, 256):
+        for amp in range(1, amps):
             if (run, amp) in listed:
                 v, n = listed[run, amp]
             else:
@@ -101,6 +107,27 @@ def _words():
 
 
 PAIR_VAL, PAIR_LEN, EOB = _words()
+
+
+# ---- the rules a test may swap (tests/test_dv_encode_edges_cpu.py does, one at a time, to show that the edge segments of
+# tests/dvenc_edges.py notice); as they stand they are the statement ----
+def mode_rule(d1, d2):
+    """2-4-8 where neighbouring lines differ much more than lines two apart"""
+    return d1 > 2 * d2 + 64
+
+
+def clip_level(lv):
+    return np.minimum(lv, 255)
+
+
+def fits(total):
+    """a segment's AC bits at a candidate quantisation number"""
+    return total <= SEGMENT_AC_BITS
+
+
+def most_bits(b):
+    """the block of a segment (its 30 bit counts) that the overflow rule takes a level from: the first with the most"""
+    return b.index(max(b))
 
 
 def shift_of(qno, cls):
@@ -142,7 +169,7 @@ def choose_mode(px, flags):
     p = px.reshape(-1, 8, 8).astype(np.int64)
     d1 = np.abs(p[:, 0:6] - p[:, 1:7]).sum(axis=(1, 2))
     d2 = np.abs(p[:, 0:6] - p[:, 2:8]).sum(axis=(1, 2))
-    return ((d1 > 2 * d2 + 64) & bool(flags & 1)).astype(np.int64)
+    return (mode_rule(d1, d2) & bool(flags & 1)).astype(np.int64)
 
 
 def transform(px, mode):
@@ -176,7 +203,7 @@ def choose_class(P, flags):
 def quantise(P, neg, cls, qno):
     """signed levels [n][64] (scan order, [:, 0] = 0) at quantisation number qno ([n] or scalar)"""
     n = FRAC + shift_of(np.broadcast_to(qno, np.shape(cls)), cls)
-    lv = np.minimum((P + (1 << (n - 1))) >> n, 255)
+    lv = clip_level((P + (1 << (n - 1))) >> n)
     lv[:, 0] = 0
     return np.where(neg, -lv, lv)
 
@@ -238,11 +265,11 @@ def encode_blocks(px, flags):
             break
         rows = np.repeat(undecided, 30)
         lv = quantise(P[rows], neg[rows], cls[rows], q)
-        fits = block_bits(lv).reshape(-1, 30).sum(axis=1) <= SEGMENT_AC_BITS
+        fit = fits(block_bits(lv).reshape(-1, 30).sum(axis=1))
         if q == 0:
-            fits[:] = True  # what does not fit at 0 goes on to the overflow rule
-        idx = np.flatnonzero(undecided)[fits]
-        lv = lv.reshape(-1, 30, 64)[fits]
+            fit[:] = True  # what does not fit at 0 goes on to the overflow rule
+        idx = np.flatnonzero(undecided)[fit]
+        lv = lv.reshape(-1, 30, 64)[fit]
         for i, one in zip(idx, lv):
             levels[30 * i:30 * i + 30] = one
         qno[idx] = q
@@ -257,7 +284,7 @@ def encode_blocks(px, flags):
         steps = 0
         while total > SEGMENT_AC_BITS:
             assert steps < 30 * 63
-            j = b.index(max(b))                      # the first block with the most bits
+            j = most_bits(b)                         # the first block with the most bits
             last = int(np.flatnonzero(lv[j])[-1])
             lv[j, last] = 0
             b[j] -= int(wl[j, last])

@@ -26,6 +26,9 @@ def picture(name):
         return np.random.default_rng(20261019).integers(0, 256, D.PICTURE_BYTES, dtype=np.uint8)
     if name == "drop":
         return E.drop_picture(S.SYS_525_60)
+    if name == "edges":  # not one of NAMES: tests/test_dv_encode_edges_cpu.py asks for it
+        import dvenc_edges
+        return dvenc_edges.picture(S.SYS_525_60)
     return D.synth(0, 1, {"flat": 0, "n8": 8, "n64": 64}[name])
 
 
