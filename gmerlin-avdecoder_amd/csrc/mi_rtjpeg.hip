@@ -56,6 +56,7 @@ struct Format {
   uint32_t mb_w, mb_h;  // macroblock, pixels (lib/RTjpeg.c:2651-2653 and 2761-2763 are these loops' steps)
   uint32_t blk_per_mb, parts, units_per_group;
   uint32_t chroma_planes, chroma_sx, chroma_sy;  // chroma planes are (w >> sx) x (h >> sy)
+  uint32_t run_tile, run_copy_threads;           // phase 2 of runs: units and lanes of a copy workgroup (RunTile)
   const char* name;
   const char* abi_name;
   const char* header_rule;  // after "packet header WxH: "
@@ -73,7 +74,7 @@ template <int Fmt>
 constexpr Format format_row(const char* name, const char* abi_name, const char* header_rule, const char* encode_rule) {
   using S = FmtShape<Fmt>;
   return {S::kMbW, S::kMbH, S::kBlkPerMb, S::kParts, S::kUnitsPerGroup, S::kChromaPlanes, S::kChromaShiftX,
-          S::kChromaShiftY, name, abi_name, header_rule, encode_rule};
+          S::kChromaShiftY, RunTile<Fmt>::kUnits, RunTile<Fmt>::kThreads, name, abi_name, header_rule, encode_rule};
 }
 constexpr Format kFormats[] = {
     format_row<kFmtYUV420>("4:2:0", "4:2:0 (MI_RTJ_FMT_YUV420)", "width and height must be positive multiples of 16", ""),
@@ -454,15 +455,14 @@ namespace {
 // for the scans, a workgroup per tile of units (4:2:0 and 4:2:2: 32 macroblocks, greyscale: 64 blocks) for the copy
 RunGrids run_grids(const mi_rtj_plan* p) {
   const Runs& r = p->runs;
-  const uint32_t tile = p->fmt == MI_RTJ_FMT_YUV422 ? RunTile<kFmtYUV422>::kUnits
-                        : p->fmt == MI_RTJ_FMT_GREY ? RunTile<kFmtGrey>::kUnits
-                                                    : (uint32_t)kRunTileMb;
-  const unsigned bx = (unsigned)(((uint64_t)kFormats[p->fmt].blk_per_mb * r.nmb_max + kRunScanThreads - 1) / kRunScanThreads);
+  const Format& F = kFormats[p->fmt];
+  const unsigned bx = (unsigned)(((uint64_t)F.blk_per_mb * r.nmb_max + kRunScanThreads - 1) / kRunScanThreads);
   RunGrids rg;
+  rg.copy_threads = F.run_copy_threads;
   rg.items = r.chunks * (uint32_t)kRunSubs;
   rg.mask = dim3(bx, std::min(r.chunks, kRunMaxGridY));
   rg.carry = dim3(bx, std::min(r.list, kRunMaxGridY));
-  rg.copy = dim3((r.nmb_max + tile - 1) / tile, std::min(rg.items, kRunMaxGridY));
+  rg.copy = dim3((r.nmb_max + F.run_tile - 1) / F.run_tile, std::min(rg.items, kRunMaxGridY));
   return rg;
 }
 

@@ -85,6 +85,36 @@ struct FmtShape<kFmtGrey> {
   static constexpr uint32_t kChromaPlanes = 0, kChromaShiftX = 0, kChromaShiftY = 0;
 };
 
+#if defined(__HIP__) || defined(__HIPCC__)
+#define MIRTJ_HD __attribute__((host, device, always_inline)) inline
+#else
+#define MIRTJ_HD inline
+#endif
+
+// Where block `k` (stream order: the luma blocks row by row, then Cb, then Cr) of unit `unit` of a w x h picture with
+// `upr` units per row lies: the byte offset of its first row relative to the Y plane (Y, then Cb, then Cr, each plane
+// packed) and the stride of its rows.  The one statement of this arithmetic for the kernels that are templates on the
+// format.
+struct BlockOrigin {
+  uint64_t off;
+  uint32_t stride;
+};
+template <int Fmt>
+MIRTJ_HD BlockOrigin block_origin(uint32_t unit, uint32_t k, uint32_t w, uint32_t h, uint32_t upr) {
+  using S = FmtShape<Fmt>;
+  constexpr uint32_t kLuma = S::kBlkPerMb - S::kChromaPlanes, kPerRow = S::kMbW / 8u;
+  const uint32_t ux = unit % upr, uy = unit / upr;
+  if (S::kChromaPlanes == 0u || k < kLuma) {
+    const uint32_t row = S::kMbH == 8u ? 0u : k / kPerRow, col = k - row * kPerRow;
+    return {(uint64_t)(uy * S::kMbH + row * 8u) * w + ux * S::kMbW + col * 8u, w};
+  }
+  const uint32_t stride = w >> S::kChromaShiftX;
+  const uint64_t ysz = (uint64_t)w * h;
+  return {ysz + (k == S::kBlkPerMb - 1u ? ysz >> (S::kChromaShiftX + S::kChromaShiftY) : 0ull) +
+              (uint64_t)(uy * (S::kMbH >> S::kChromaShiftY)) * stride + ux * (S::kMbW >> S::kChromaShiftX),
+          stride};
+}
+
 // zig-zag order of the bitstream, transposed relative to JPEG (lib/RTjpeg.c:59-74)
 #define MIRTJ_ZZ_INIT                                                                        \
   {0,  8,  1,  2,  9,  16, 24, 17, 10, 3,  4,  11, 18, 25, 32, 40, 33, 26, 19, 12, 5,  6,   \

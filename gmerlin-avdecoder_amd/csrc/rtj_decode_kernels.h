@@ -206,13 +206,21 @@ __device__ __forceinline__ uint32_t walk_record(const FrameDev& f, const uint8_t
 //   * a block is ONE straight path: the next position is selected between its two cases (unchanged block: 1 byte; else
 //     behind the byte whose weight sum reaches the target — tables whose blocks are all raw bytes are refused by the host,
 //     kMaxRawBytes) with scalar selects, and both windows are searched at once;
-//   * the macroblock's six blocks are unrolled, so the raw-byte count of a block is a loop constant;
+//   * the macroblock's blocks are unrolled from FmtShape<Fmt> (kBlkPerMb - kChromaPlanes luma steps, then kChromaPlanes
+//     chroma steps: Y Y Y Y Cb Cr, Y Y Cb Cr, or Y alone), so the raw-byte count of a block is a loop constant;
 //   * of the window's bytes only "is 0xFF" is kept, as a lane mask in scalar registers (one compare per 64 bytes instead of
 //     a lane read per block), so nothing but the weight sums and the bytes in flight rotates when the window slides;
 //   * the stream is read through a buffer descriptor that returns 0 past the packet's end (no exec masking);
 //   * the offsets are gathered with v_writelane at a running lane and stored 64 at a time.
+// Bounds no stream reaches, for all three block patterns: the search of a block is entered with lp < 64, and a block is
+// at most 64 bytes (the host refuses tables with more than kMaxRawBytes raw coefficients, so a block always ends behind
+// a byte of the two windows), so the next lp is at most 127 and the slide loop runs at most once per block; the
+// macroblock loop runs f.nmb times.
+template <int Fmt>
 __device__ __forceinline__ void walk_packet(const FrameDev& f, const uint8_t* __restrict__ stream,
                                             const QTab* __restrict__ lut, uint32_t* __restrict__ out) {
+  constexpr uint32_t kB = FmtShape<Fmt>::kBlkPerMb, kLuma = kB - FmtShape<Fmt>::kChromaPlanes;
+  static_assert((kLuma == 1u || kLuma == 2u || kLuma == 4u) && (kB == kLuma || kB == kLuma + 2u), "the step list below");
   const uint32_t lane = threadIdx.x & 63u;
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc((void*)(stream + f.data_off), 0, (int)f.data_len, 0x00020000);
@@ -278,14 +286,20 @@ __device__ __forceinline__ void walk_packet(const FrameDev& f, const uint8_t* __
     asm("s_bitcmp1_b64 %1, %2\n\ts_cselect_b32 %0, %3, %4" : "=s"(lp) : "s"(ffc), "s"(lp), "s"(lp + 1u), "s"(e + 1u) : "scc");
   };
   for (uint32_t mb = 0; mb < f.nmb; ++mb) {
-    if (j > 58u) flush();
+    if (j > 64u - kB) flush();
+    // kLuma (4, 2 or 1) luma steps, then the chroma pair.  Written out: as a loop over the block number, unrolled by
+    // the compiler, every step of the 4:2:0 walker compiles to one more scalar instruction.
     step(lb8, need_l, 0);
-    step(lb8, need_l, 1);
-    step(lb8, need_l, 2);
-    step(lb8, need_l, 3);
-    step(cb8, need_c, 4);
-    step(cb8, need_c, 5);
-    j += 6u;
+    if constexpr (kLuma > 1u) step(lb8, need_l, 1);
+    if constexpr (kLuma > 2u) {
+      step(lb8, need_l, 2);
+      step(lb8, need_l, 3);
+    }
+    if constexpr (kB > kLuma) {
+      step(cb8, need_c, (int)kLuma);
+      step(cb8, need_c, (int)kLuma + 1);
+    }
+    j += kB;
   }
   if (j > 63u) flush();
   asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(acc) : "s"(base + lp), "s"(j) : "m0");  // the end
@@ -299,7 +313,7 @@ __global__ __launch_bounds__(64) void k_index_walk(const FrameDev* __restrict__ 
                                                     const QTab* __restrict__ lut,
                                                     uint32_t* __restrict__ blkoff) {
   const FrameDev f = frames[blockIdx.x];
-  walk_packet(f, stream, lut, blkoff + f.blk_base);
+  walk_packet<kFmtYUV420>(f, stream, lut, blkoff + f.blk_base);
 }
 
 // The packets of a to-do list, a wave each (grid-stride): what k_spec_policy hands the serial walker when the list is long.
@@ -311,7 +325,7 @@ __global__ __launch_bounds__(64) void k_index_walk_todo(const FrameDev* __restri
   const uint32_t n = *ntodo;
   for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
     const FrameDev f = frames[todo[i]];
-    walk_packet(f, stream, lut, blkoff + f.blk_base);
+    walk_packet<kFmtYUV420>(f, stream, lut, blkoff + f.blk_base);
   }
 }
 

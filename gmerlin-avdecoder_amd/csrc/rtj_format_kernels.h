@@ -3,8 +3,8 @@
 //   RTjpeg_decompressYUV422 (lib/RTjpeg.c:2639-2686)  macroblock = 16x8 pixels: Y, Y, Cb, Cr; chroma planes w/2 x h
 //   RTjpeg_decompress8      (lib/RTjpeg.c:2751-2772)  8x8 luma blocks in raster order, one plane
 //
-//   k_index_fmt<Fmt>    block-start index: walk_packet (rtj_decode_kernels.h) with the format's block pattern as a
-//                       compile-time list, one wave per packet, packets side by side (grid-stride).
+//   k_index_fmt<Fmt>    block-start index: walk_packet<Fmt> (rtj_decode_kernels.h), one wave per packet, packets side by
+//                       side (grid-stride).
 //   k_decode_fmt<Fmt>   dequantise + inverse transform + plane scatter, one lane per 8x8 block, one wave per part of a
 //                       group.  The arithmetic is the 4:2:0 path's: the packed passes of rtj_idct_pk.h behind their
 //                       per-block range test, the one-value-per-register passes of rtj_idct_asm.h as the fallback,
@@ -22,97 +22,6 @@
 
 namespace mirtj {
 
-// ---------------------------------------------------------------------------------------
-// walk_packet_fmt: walk_packet (rtj_decode_kernels.h:214-294) for the format's macroblock.  One wave, the position in
-// scalar registers, both windows searched at once, one straight path per block; the macroblock's blocks are unrolled
-// from the compile-time pattern, so a block's raw-byte count is a loop constant.  The host refuses tables with more
-// than kMaxRawBytes raw coefficients, so a block always ends behind a byte of the two windows.
-// Bounds no stream reaches: a block is at most 64 bytes, so its successor starts at most 128 bytes behind the window's
-// base (63 + 64 + 1) and the window slides at most twice per block; the macroblock loop runs f.nmb times.
-// ---------------------------------------------------------------------------------------
-template <int Fmt>
-__device__ __forceinline__ void walk_packet_fmt(const FrameDev& f, const uint8_t* __restrict__ stream,
-                                                const QTab* __restrict__ lut, uint32_t* __restrict__ out) {
-  constexpr uint32_t kB = FmtShape<Fmt>::kBlkPerMb;
-  const uint32_t lane = threadIdx.x & 63u;
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(stream + f.data_off), 0, (int)f.data_len, 0x00020000);
-  // a stream byte as int8; the descriptor returns 0 at or past the packet's end
-  auto fetch = [&](uint32_t pos) -> int {
-    return (int)(int8_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(pos + lane), 0, 0);
-  };
-  auto weight = [](int b) -> uint32_t {  // token_weight() of an int8
-    const int x = b - 63;
-    return (uint32_t)(x < 1 ? 1 : x > 64 ? 64 : x);
-  };
-  const uint32_t lb8 = (uint32_t)lut[f.qidx].lb8, cb8 = (uint32_t)lut[f.qidx].cb8;
-  const uint32_t need_l = 63u - lb8, need_c = 63u - cb8;
-  uint32_t base = 0, Wc, Wn;
-  int pf1, pf2, pf3;
-  unsigned long long ffc, ffn;  // lanes of the two windows that hold 0xFF
-  {
-    const int cur = fetch(0u), nxt = fetch(64u);
-    pf1 = fetch(128u);
-    pf2 = fetch(192u);
-    pf3 = fetch(256u);
-    Wc = wave_incl_scan(weight(cur));
-    Wn = wave_incl_scan(weight(nxt)) + (uint32_t)__builtin_amdgcn_readlane((int)Wc, 63);
-    ffc = __ballot(cur == -1);
-    ffn = __ballot(nxt == -1);
-  }
-  uint32_t lp = 0;  // the current block's start, relative to base
-  uint32_t j = 0;   // offsets gathered in acc since the last store
-  uint32_t acc = 0;
-  uint32_t* o = out;  // where acc's lane 0 goes
-  auto flush = [&]() {
-    if (lane < j) o[lane] = acc;
-    o += j;
-    j = 0;
-  };
-  auto step = [&](const uint32_t bt8, const uint32_t need, const int c) {  // c: the block's number in its macroblock
-    for (int s = 0; s < 2 && lp >= 64u; s++) {  // slide the two windows forward (lp <= 128: twice at the most)
-      base += 64u;
-      lp -= 64u;
-      const int b = pf1;
-      pf1 = pf2;
-      pf2 = pf3;
-      pf3 = fetch(base + 256u);
-      Wc = Wn;
-      ffc = ffn;
-      Wn = wave_incl_scan(weight(b)) + (uint32_t)__builtin_amdgcn_readlane((int)Wc, 63);
-      ffn = __ballot(b == -1);
-    }
-    asm("s_add_i32 m0, %2, %3\n\tv_writelane_b32 %0, %1, m0" : "+v"(acc) : "s"(base + lp), "s"(j), "n"(c) : "m0", "scc");
-    const uint32_t iq = lp + bt8;  // last non-token byte of the block, 0..78
-    const uint32_t wq_c = (uint32_t)__builtin_amdgcn_readlane((int)Wc, (int)(iq & 63u));
-    const uint32_t wq_n = (uint32_t)__builtin_amdgcn_readlane((int)Wn, (int)(iq & 63u));
-    const uint32_t target = (iq < 64u ? wq_c : wq_n) + need;
-    const unsigned long long mc = __ballot(Wc >= target), mn = __ballot(Wn >= target);
-    uint32_t ec, en;
-    asm("s_ff1_i32_b64 %0, %1" : "=s"(ec) : "s"(mc));
-    asm("s_ff1_i32_b64 %0, %1" : "=s"(en) : "s"(mn));
-    en |= 64u;
-    const uint32_t e = ec < en ? ec : en;
-    asm("s_bitcmp1_b64 %1, %2\n\ts_cselect_b32 %0, %3, %4" : "=s"(lp) : "s"(ffc), "s"(lp), "s"(lp + 1u), "s"(e + 1u) : "scc");
-  };
-  for (uint32_t mb = 0; mb < f.nmb; ++mb) {
-    if (j > 64u - kB) flush();
-    if (Fmt == kFmtYUV422) {
-      step(lb8, need_l, 0);
-      step(lb8, need_l, 1);
-      step(cb8, need_c, 2);
-      step(cb8, need_c, 3);
-    } else {
-      step(lb8, need_l, 0);
-    }
-    j += kB;
-  }
-  if (j > 63u) flush();
-  asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(acc) : "s"(base + lp), "s"(j) : "m0");  // the end
-  j += 1u;
-  flush();
-}
-
 // The packets of a plan, a wave each, side by side (grid-stride over the packets as in k_index_walk_todo).
 template <int Fmt>
 __global__ __launch_bounds__(64) void k_index_fmt(const FrameDev* __restrict__ frames, uint32_t nframes,
@@ -120,7 +29,7 @@ __global__ __launch_bounds__(64) void k_index_fmt(const FrameDev* __restrict__ f
                                                    uint32_t* __restrict__ blkoff) {
   for (uint32_t i = blockIdx.x; i < nframes; i += gridDim.x) {
     const FrameDev f = frames[i];
-    walk_packet_fmt<Fmt>(f, stream, lut, blkoff + f.blk_base);
+    walk_packet<Fmt>(f, stream, lut, blkoff + f.blk_base);
   }
 }
 

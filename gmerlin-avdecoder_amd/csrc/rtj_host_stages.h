@@ -119,7 +119,7 @@ void launch_spec_walk(bool two_types, int spec_mode, uint32_t* state, dim3 grid,
 
 struct RunGrids {
   dim3 mask, carry, copy;
-  uint32_t items;
+  uint32_t items, copy_threads;
 };
 int stage_runs(Launch& L, bool runs, const RunGrids& g, uint8_t* out);
 
@@ -357,9 +357,17 @@ int stage_transform_classic(Launch& L, const Transform& T, bool all_parts) {
 
 // ---- stage 6: phase 2 of a plan with runs: unchanged blocks from the run's earlier pictures, read from this launch's index ----
 // (the three kernels of the plan's format; one set of books: run_ev, and launch_close / launch_fmt note runs_ran)
-int stage_runs(Launch& L, bool runs, const RunGrids& g, uint8_t* out) {
+template <int Fmt>
+void queue_runs(Launch& L, const RunGrids& g, uint8_t* out) {
   mi_rtj_plan* p = L.p;
   const Runs& r = p->runs;
+  hipLaunchKernelGGL(k_runs_mask<Fmt>, g.mask, dim3(kRunScanThreads), 0, L.ds, p->d_frames, r.d_chunks, r.chunks, (const uint32_t*)L.blk, r.d_mask);
+  hipLaunchKernelGGL(k_runs_carry<Fmt>, g.carry, dim3(kRunScanThreads), 0, L.ds, r.d_runs, r.list, r.d_chunks, r.d_mask, r.d_carry, r.d_copied);
+  hipLaunchKernelGGL(k_runs_copy<Fmt>, g.copy, dim3(g.copy_threads), 0, L.ds, p->d_frames, r.d_chunks, g.items, r.d_mask, r.d_carry, out, r.d_copied);
+}
+
+int stage_runs(Launch& L, bool runs, const RunGrids& g, uint8_t* out) {
+  mi_rtj_plan* p = L.p;
   if (p->profile) {
     Timed rt;
     rt.a = L.clk.prev;
@@ -368,18 +376,10 @@ int stage_runs(Launch& L, bool runs, const RunGrids& g, uint8_t* out) {
     p->run_ev.push_back(rt);
   }
   if (!runs) return MI_RTJ_OK;
-  if (p->fmt == MI_RTJ_FMT_YUV422) {
-    hipLaunchKernelGGL(k_runs_mask_fmt<kFmtYUV422>, g.mask, dim3(kRunScanThreads), 0, L.ds, p->d_frames, r.d_chunks, r.chunks, (const uint32_t*)L.blk, r.d_mask);
-    hipLaunchKernelGGL(k_runs_carry_fmt<kFmtYUV422>, g.carry, dim3(kRunScanThreads), 0, L.ds, r.d_runs, r.list, r.d_chunks, r.d_mask, r.d_carry, r.d_copied);
-    hipLaunchKernelGGL(k_runs_copy_fmt<kFmtYUV422>, g.copy, dim3(RunTile<kFmtYUV422>::kThreads), 0, L.ds, p->d_frames, r.d_chunks, g.items, r.d_mask, r.d_carry, out, r.d_copied);
-  } else if (p->fmt == MI_RTJ_FMT_GREY) {
-    hipLaunchKernelGGL(k_runs_mask_fmt<kFmtGrey>, g.mask, dim3(kRunScanThreads), 0, L.ds, p->d_frames, r.d_chunks, r.chunks, (const uint32_t*)L.blk, r.d_mask);
-    hipLaunchKernelGGL(k_runs_carry_fmt<kFmtGrey>, g.carry, dim3(kRunScanThreads), 0, L.ds, r.d_runs, r.list, r.d_chunks, r.d_mask, r.d_carry, r.d_copied);
-    hipLaunchKernelGGL(k_runs_copy_fmt<kFmtGrey>, g.copy, dim3(RunTile<kFmtGrey>::kThreads), 0, L.ds, p->d_frames, r.d_chunks, g.items, r.d_mask, r.d_carry, out, r.d_copied);
-  } else {
-    hipLaunchKernelGGL(k_runs_mask, g.mask, dim3(kRunScanThreads), 0, L.ds, p->d_frames, r.d_chunks, r.chunks, (const uint32_t*)L.blk, r.d_mask);
-    hipLaunchKernelGGL(k_runs_carry, g.carry, dim3(kRunScanThreads), 0, L.ds, r.d_runs, r.list, r.d_chunks, r.d_mask, r.d_carry, r.d_copied);
-    hipLaunchKernelGGL(k_runs_copy, g.copy, dim3(kRunCopyThreads), 0, L.ds, p->d_frames, r.d_chunks, g.items, r.d_mask, r.d_carry, out, r.d_copied);
+  switch (p->fmt) {
+    case MI_RTJ_FMT_YUV422: queue_runs<kFmtYUV422>(L, g, out); break;
+    case MI_RTJ_FMT_GREY: queue_runs<kFmtGrey>(L, g, out); break;
+    default: queue_runs<kFmtYUV420>(L, g, out); break;
   }
   if (p->profile) HIPCHK(L.c, hipEventRecord(p->run_ev.back().b, L.ds));
   return MI_RTJ_OK;

@@ -236,8 +236,8 @@ int mi_rtj_plan_set_runs(mi_rtj_plan *plan, int n_runs, const int *run_len);
 /* Runs on a plan of any format (the output of mi_rtj_encode_stream_fmt decoded in one launch).  On a 4:2:0 plan it is
  * mi_rtj_plan_set_runs: the same kernels and buffers.  On a 4:2:2 or greyscale plan the semantics, the refusals and the
  * queries below are the same, "block b" is in the format's stream order (4:2:2: Y, Y, Cb, Cr per 16 x 8 macroblock,
- * lib/RTjpeg.c:2639-2686; greyscale: raster order, :2751-2772), and the three run kernels are the format's forms
- * (k_runs_*_fmt, rtj_runs_kernels.h), queued behind the transform on the instance's stream. */
+ * lib/RTjpeg.c:2639-2686; greyscale: raster order, :2751-2772), and the three run kernels are the format's instances
+ * (k_runs_mask / k_runs_carry / k_runs_copy<Fmt>, rtj_runs_kernels.h), queued behind the transform on the instance's stream. */
 int mi_rtj_plan_set_runs_fmt(mi_rtj_plan *plan, int n_runs, const int *run_len);
 /* While profiling (mi_rtj_plan_profile): device time of the run kernels summed over the decodes since profiling was
  * switched on, *launches = decodes that ran them.  (mi_rtj_plan_times keeps its kernels; mi_rtj_plan_step_times ends

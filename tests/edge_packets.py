@@ -82,17 +82,19 @@ def adversarial_packets(seed=2025):
 CHUNK_CASES = [(255, "long"), (255, "skip"), (255, "mix"), (100, "long"), (100, "mix"), (255, "runs")]
 
 
-def chunk_boundary_packets(seed=77, w=1024, h=256, cases=CHUNK_CASES):
+def chunk_boundary_packets(seed=77, w=1024, h=256, cases=CHUNK_CASES, pattern=(16, 16, 4, 2)):
     """maximal 64-byte blocks (no zero runs), minimal 1-byte (0xFF) blocks, and mixtures, so macroblocks straddle every
-    chunk boundary differently (1024x256: long-block packets span ~110 chunks)"""
+    chunk boundary differently (1024x256: long-block packets span ~110 chunks).  pattern: the format's unit as (width,
+    height, luma blocks, chroma blocks) — 4:2:0's Y Y Y Y Cb Cr unless said otherwise; lb8 / cb8 raw bytes by block type"""
     rng = np.random.default_rng(seed)
-    nblk = (w // 16) * (h // 16) * 6
+    uw, uh, nluma, nchroma = pattern
+    nblk = (w // uw) * (h // uh) * (nluma + nchroma)
     pkts = []
     for Q, mode in cases:
         _, _, lb8, cb8, _, _ = R.oracle_tables(Q)
         body = bytearray()
         for b in range(nblk):
-            bt8 = lb8 if (b % 6) < 4 else cb8
+            bt8 = lb8 if (b % (nluma + nchroma)) < nluma else cb8
             kind = mode if mode != "mix" else ["long", "skip", "short", "runs"][int(rng.integers(0, 4))]
             if kind == "skip":
                 body.append(255)
@@ -111,6 +113,17 @@ def chunk_boundary_packets(seed=77, w=1024, h=256, cases=CHUNK_CASES):
             body += bytes(blk)
         pkts.append(packet_from_body(w, h, Q, body))
     return pkts
+
+
+# the same for the serial walker of the other two formats (MI_RTJ_FMT_*: 1 = 4:2:2, Y Y Cb Cr; 2 = greyscale, luma only),
+# at sizes where it stores its gathered offsets more than once and the last store is partial: 132 and 153 blocks
+FORMAT_BOUNDARY_SHAPES = {1: (176, 24, (16, 8, 2, 2)), 2: (136, 72, (8, 8, 1, 0))}
+
+
+def format_boundary_packets(fmt, seed=78):
+    """CHUNK_CASES' six packets (long, skip, mix and runs at Q 255; long and mix at Q 100) in the format's block pattern"""
+    w, h, pattern = FORMAT_BOUNDARY_SHAPES[fmt]
+    return chunk_boundary_packets(seed=seed, w=w, h=h, pattern=pattern)
 
 
 # --------------------------------------------------------------------------- the low-4x4 forms and their boundary

@@ -5,6 +5,7 @@ Run on the GPU box with `pytest -m gpu`."""
 import numpy as np
 import pytest
 
+import edge_packets as E
 import rtjfmt as F
 import rtjlib as R
 from pkg import P
@@ -272,6 +273,16 @@ def test_packets_cut_in_the_middle_of_a_block(fmt, w, h):
     cuts = [F.HEADER + int(offs[k]) + d for k, d in ((1, 0), (5, 1), (offs.size // 2, 7), (offs.size - 2, 3))] + [F.HEADER, 5]
     plan_decode_each(fmt, [pkt[:c].copy() for c in cuts if c >= F.HEADER])
     # (a packet shorter than its header is refused by the one-packet path and zero-padded by a plan's caller: not a stream)
+
+
+@pytest.mark.parametrize("fmt", (F.FMT_422, F.FMT_GREY))
+def test_packets_of_longest_and_shortest_blocks(fmt):
+    """the serial walker's window slide and offset stores: 64-byte blocks, 1-byte blocks, run tokens and their mixtures
+    in the format's block pattern (tests/edge_packets.py; tests/test_rtjfmt_cpu.py holds the expectation to the
+    reference's own decoder)"""
+    pkts = E.format_boundary_packets(fmt)
+    assert len(pkts) == 6 and F.nblocks(fmt, *F.header_of(pkts[0])[:2]) in (132, 153)
+    plan_decode_each(fmt, pkts)
 
 
 @pytest.mark.parametrize("fmt,w,h", [(F.FMT_422, 176, 40), (F.FMT_GREY, 136, 72)])

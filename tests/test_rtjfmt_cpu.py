@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import edge_packets as E
 import rtjfmt as F
 import rtjlib as R
 from pkg import P, ROOT
@@ -59,6 +60,27 @@ def test_restatement_equals_the_live_reference(fmt, w, h):
                     assert first_diff(got, want) is None, (Q, amp, key, i, first_diff(got, want))
                     pictures += 1
     assert pictures == 90
+
+
+@needs_ref
+@pytest.mark.parametrize("fmt", (F.FMT_422, F.FMT_GREY))
+def test_restatement_equals_the_live_reference_on_boundary_packets(fmt):
+    """the packets tests/test_gpu_rtjfmt.py sends through the serial walker (64-byte blocks, 1-byte blocks, run tokens):
+    what the device is compared with there is the reference's own picture here"""
+    pkts = E.format_boundary_packets(fmt)
+    assert len(pkts) == 6
+    lens = []
+    for i, pkt in enumerate(pkts):
+        w, h, _ = F.header_of(pkt)
+        want = np.full(F.plane_bytes(fmt, w, h), 0x4D, np.uint8)
+        got = want.copy()
+        F.RefFmt(fmt).decode(pkt, want)
+        used, offs = F.Restated(fmt).decode(pkt, got)
+        assert used == pkt.size and offs.size == F.nblocks(fmt, w, h) + 1 and offs[-1] == pkt.size - F.HEADER, i
+        assert first_diff(got, want) is None, (i, first_diff(got, want))
+        lens.append(np.diff(offs.astype(np.int64)))
+    lens = np.concatenate(lens)
+    assert lens.min() == 1 and lens.max() == 64  # the set holds the shortest and the longest block there is
 
 
 @needs_ref

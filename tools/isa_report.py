@@ -8,9 +8,13 @@ code object's metadata says (VGPR / SGPR count, scalar-register spills, LDS byte
 static census of the instruction stream: vector / scalar / LDS / vector-memory instructions and —
 the figure VERDICT r2 asked to track — v_readlane_b32 / v_writelane_b32 (scalar spills are paid in
 those).  Numbers are static (program text), not dynamic counts.  --digest adds a hash of each kernel's instruction
-text (branch labels renumbered, comments dropped), so that two builds can be shown to compile a kernel to the same
-code; --src compiles another checkout's csrc/ (e.g. the parent commit's) with this tool; --bodies writes that instruction
-text of the selected kernels to a file, so that `diff` can compare two builds line by line."""
+text, so that two builds can be shown to compile a kernel to the same code.  What is hashed: the kernel's instruction
+lines and its labels, in order, with comments dropped and branch labels renumbered.  Lines that begin with `.` and are
+no label (assembler directives: .amdhsa_kernel <mangled name>, .section .text.<mangled name>, the kernel descriptor)
+are left out, so a kernel that is renamed or becomes a template instance keeps its hash when its code is the same; the
+register, spill, LDS and scratch figures come from the metadata and are printed beside the hash.  --src compiles another
+checkout's csrc/ (e.g. the parent commit's) with this tool; --bodies writes the hashed text of the selected kernels to a
+file, so that `diff` can compare two builds line by line."""
 import argparse
 import hashlib
 import json
@@ -117,7 +121,9 @@ def parse(path):
             elif op.startswith(("global_", "buffer_", "flat_", "scratch_")):
                 c["vmem"] += 1
         body = [re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s*;.*$", "", ln.strip())) for ln in v["lines"]]
-        body = [x for x in body if x]
+        # instructions and labels only: directives (.amdhsa_kernel <name>, .section .text.<name>, .p2align ...) carry
+        # the kernel's mangled name and its descriptor, which the resource figures below report from the metadata
+        body = [x for x in body if x and (not x.startswith(".") or x.endswith(":"))]
         digest = hashlib.sha1("\n".join(body).encode()).hexdigest()[:16]
         m = meta[k]
         rep[k] = {"digest": digest, "body": body, "vgpr": int(m.get("vgpr_count", 0)), "sgpr": int(m.get("sgpr_count", 0)),
