@@ -557,10 +557,146 @@ __global__ __launch_bounds__(64) void k_spec_walk_any(const FrameDev* __restrict
     spec_walk_body<PHASE, kSpecLeadVery>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
 }
 
+// ---- k_spec_verify's emission where the launch's walkers walked runs: the RUN is the unit ----
+// A run walker's bits are one long span.  Cut into chunks, every chunk cost two dword loads per lane (80 of 128
+// lane-dwords in use at most), two wave scans and a turn of the LDS window, and a chunk's 16-byte pieces lie 1 KB apart.
+// A wave takes a whole run instead: its blocks are numbered from the base of the run's first chunk, as many as its
+// chunks count together (inside a run hand.y of a chunk and hand.x of the next are one record: the counts are
+// contiguous), and its bits are read once, a 16-byte piece per lane from the piece that holds the first chunk's
+// hand-over point (at most a macroblock, 384 bytes, before it) to the end of the run's last chunk — 51 pieces at most at
+// S = 3, 67 at S = 4: the pieces past the 64th are a second, mostly idle load.  One popcount scan ranks them.
+constexpr int kSpecVerRunWindow = 1024;  // ranks a wave orders in LDS at a time (a run of ordinary content: ~200 per chunk)
+static_assert(spec_run_tiles((uint32_t)kSpecRunMax) <= 128u, "a run walker's bits: two 16-byte pieces per lane");
+static_assert(kSpecLead + kSpecRunMax * kSpecChunk < 65536, "run-relative positions are 16 bits in the window");
+
+struct SpecVerRun {
+  uint32_t m;      // blocks to emit (clipped to the packet's own index); 0: nothing to do
+  uint32_t base;   // the first one's number within the packet
+  uint32_t first;  // the hand-over point of the run's first chunk, relative to the run walker's first byte
+  uint32_t start;  // the run walker's first byte, relative to the packet's
+  uint32_t p0, pend;  // pieces [p0, pend) of the walker's bits are looked at
+  uint4 w, t;      // the lane's piece p0 + lane, and p0 + 64 + lane (zero past pend)
+};
+
+// The starts of one piece in rank order into the window: bit 31 - i of dword d is the byte at q + 32 d + i, the lane's
+// first start has rank rk (window-relative, may be negative or past the window).  The four dwords are four independent
+// chains, and the loop runs for the fullest DWORD of the wave (4-5 starts where a macroblock's chroma blocks lie, 2 in
+// luma), not for the fullest lane.  `many`: the run takes more than one window — dwords that have nothing in this one
+// are dropped first, so that a window costs what it holds.
+__device__ __forceinline__ void spec_ver_scatter(uint16_t* __restrict__ sp, const uint4 w, int rk, const uint32_t q,
+                                                 const uint32_t span_, const bool many) {
+  uint32_t mk[4] = {w.x, w.y, w.z, w.w};
+  int r[4];
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    r[d] = rk;
+    rk += __builtin_popcount(mk[d]);
+  }
+  if (many) {
+#pragma unroll
+    for (int d = 0; d < 4; d++)
+      if (r[d] >= (int)span_ || r[d] + __builtin_popcount(mk[d]) <= 0) mk[d] = 0u;
+  }
+  while (__any((mk[0] | mk[1] | mk[2] | mk[3]) != 0u)) {
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+      if (mk[d]) {
+        const int z = __builtin_clz(mk[d]);  // bit 31 is the dword's first byte
+        if ((uint32_t)r[d] < span_) sp[r[d]] = (uint16_t)(q + 32u * (uint32_t)d + (uint32_t)z);
+        r[d]++;
+        mk[d] &= ~(0x80000000u >> z);
+      }
+    }
+  }
+}
+
+// One tile of k_spec_verify, after its scan: s_base / s_cnt / s_i0 hold the tile's chunks, the tile starts with a run
+// (the tile loop steps by whole runs) — run number run0 of the packet — and holds tile_n chunks.  The workgroup's waves
+// take consecutive runs in the same step: a piece of eight neighbouring run walkers is one 128-byte line, asked for by
+// one CU at one time.  While a wave orders a run, the bits of its next one are on their way.  Nothing on this path
+// divides.  (Emitting a run one of whose walkers is about to be walked again is harmless, as emitting such a chunk was:
+// the second pass emits the whole packet again, chunk by chunk, from wherever each chunk's bits are by then.)
+__device__ __forceinline__ void spec_ver_emit_runs(uint16_t* __restrict__ sp, const uint32_t* __restrict__ s_i0,
+                                                   const uint32_t* __restrict__ s_base, const uint32_t* __restrict__ s_cnt,
+                                                   const uint32_t tile_n, const uint32_t run0, const uint32_t wk0,
+                                                   const SpecRunArgs& ra, const uint32_t last, uint32_t* __restrict__ out,
+                                                   const int lane, const uint32_t wv) {
+  constexpr uint32_t kWaves = kSpecVerThreads / 64;
+  const uint32_t S = ra.S, tiles = spec_run_tiles(S);
+  const uint4* const rows = (const uint4*)ra.runbits;  // [wave of walkers][tile][lane]: a piece is one uint4
+  auto fetch = [&](const uint32_t jr, SpecVerRun& R) {
+    const uint32_t j = jr * S;  // the run's first chunk, within the tile
+    R.m = 0u;
+    R.w = R.t = make_uint4(0u, 0u, 0u, 0u);
+    if (j >= tile_n) return;  // wave-uniform, as all of this is but the loads
+    const uint32_t nch = min(S, tile_n - j);
+    uint32_t cnt = 0;
+    for (uint32_t k = 0; k < nch; k++) cnt += s_cnt[j + k];
+    cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)cnt);
+    R.base = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_base[j]);
+    R.first = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_i0[j]);
+    R.m = R.base <= last ? min(cnt, last + 1u - R.base) : 0u;  // clipped to the packet's own index
+    const uint32_t r = run0 + jr;  // the run's number within the packet: its walker's first byte follows from it
+    R.start = r ? r * S * (uint32_t)kSpecChunk - (uint32_t)kSpecLead : 0u;
+    R.p0 = R.first / (uint32_t)kSpecTile;
+    R.pend = min(tiles, ((r * S + nch) * (uint32_t)kSpecChunk - R.start) / (uint32_t)kSpecTile);
+    if (R.m == 0u) return;
+    const uint32_t wk = wk0 + r;
+    const uint4* const row = rows + (size_t)(wk >> 6) * tiles * 64u + (wk & 63u);
+    const uint32_t pa = R.p0 + (uint32_t)lane, pb = pa + 64u;
+    if (pa < R.pend) R.w = row[(size_t)pa * 64u];
+    if (pb < R.pend) R.t = row[(size_t)pb * 64u];
+  };
+  SpecVerRun R, N;
+  fetch(wv, R);
+  for (uint32_t jr = wv; jr * S < tile_n; jr += kWaves, R = N) {
+    fetch(jr + kWaves, N);
+    if (R.m == 0u) continue;  // wave-uniform
+    if (lane == 0) {  // starts before the hand-over point (bit 31 = a dword's first byte)
+      const int fo = (int)(R.first % (uint32_t)kSpecTile);
+      uint32_t* const wd[4] = {&R.w.x, &R.w.y, &R.w.z, &R.w.w};
+#pragma unroll
+      for (int d = 0; d < 4; d++) {
+        const int sh = fo - 32 * d;
+        if (sh >= 32) *wd[d] = 0u;
+        else if (sh > 0) *wd[d] &= 0xFFFFFFFFu >> sh;
+      }
+    }
+    const uint32_t pc = (uint32_t)(__builtin_popcount(R.w.x) + __builtin_popcount(R.w.y) + __builtin_popcount(R.w.z) +
+                                   __builtin_popcount(R.w.w));
+    const uint32_t incl = wave_incl_scan(pc);
+    const bool tailed = R.pend > R.p0 + 64u;  // S = 4 only: up to three more pieces
+    uint32_t rkt = 0;
+    if (tailed) {
+      const uint32_t pt = (uint32_t)(__builtin_popcount(R.t.x) + __builtin_popcount(R.t.y) + __builtin_popcount(R.t.z) +
+                                     __builtin_popcount(R.t.w));
+      rkt = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63) + wave_incl_scan(pt) - pt;
+    }
+    const uint32_t q = (R.p0 + (uint32_t)lane) * (uint32_t)kSpecTile;  // run-relative position of the piece's first byte
+    uint32_t* const o = out + R.base;
+    const bool many = R.m > (uint32_t)kSpecVerRunWindow;
+    // in rank order in LDS, out as whole 256-byte rows, as the chunks' starts leave (k_spec_verify)
+    for (uint32_t r0 = 0; r0 < R.m; r0 += (uint32_t)kSpecVerRunWindow) {
+      const uint32_t span_ = min((uint32_t)kSpecVerRunWindow, R.m - r0);
+      spec_ver_scatter(sp, R.w, (int)(incl - pc) - (int)r0, q, span_, many);
+      if (tailed) spec_ver_scatter(sp, R.t, (int)rkt - (int)r0, q + 64u * (uint32_t)kSpecTile, span_, many);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (uint32_t k = (uint32_t)lane; k < span_; k += 64u) o[r0 + k] = R.start + (uint32_t)sp[k];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  }
+}
+
 // One workgroup per packet: the chain check, the block numbering, and — the numbering is all it needs —
 // the block-offset index itself.  A packet that fails goes on the exact kernels' to-do list (they then
 // rewrite its index).
-// RUNS: a plan with runs (a kernel of its own: the other plans' is the one it was).
+// RUNS: a plan with runs (a kernel of its own: the other plans' is the one it was).  Its first pass over walkers that
+// walked runs keeps the proof per chunk and emits per run (spec_ver_emit_runs); its second pass, and a launch whose state
+// names a longer lead, emit per chunk as the other plans' kernel does.
 template <bool RUNS>
 __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev* __restrict__ frames,
                                                       const uint32_t* __restrict__ spec_base,
@@ -580,7 +716,8 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
   if (pass == 2 && ok[blockIdx.x] != 2u) return;  // the second pass only looks at packets with repaired chunks
   __shared__ uint32_t s_wave[kSpecVerThreads / 64], s_carry[3];  // carry: [1] blocks so far, [2] bad
   __shared__ uint32_t s_i0[kSpecVerThreads], s_base[kSpecVerThreads], s_cnt[kSpecVerThreads];
-  __shared__ uint16_t s_pos[kSpecVerThreads / 64][kSpecVerWindow];  // per wave: block offsets in rank order, on their way out
+  constexpr int kWindow = RUNS ? kSpecVerRunWindow : kSpecVerWindow;  // (the emission per chunk uses kSpecVerWindow of it)
+  __shared__ uint16_t s_pos[kSpecVerThreads / 64][kWindow];  // per wave: block offsets in rank order, on their way out
   const FrameDev f = frames[blockIdx.x];
   const uint32_t sc0 = spec_base[blockIdx.x], nsc = spec_base[blockIdx.x + 1] - sc0;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -596,10 +733,20 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
     s_carry[2] = 0;
   }
   __syncthreads();
-  for (uint32_t c0 = 0; c0 < nsc; c0 += kSpecVerThreads) {
+  // Emission per run (first pass over run walkers): a tile is the most whole runs that 512 chunks hold, so that every run
+  // lies in one tile (the one division of the kernel; a packet's runs start at chunk 0 and are S chunks each but the last)
+  const bool by_run = RUNS && pass == 1 && run_walkers;
+  uint32_t tile_runs = 0, tile_step = (uint32_t)kSpecVerThreads;
+  if constexpr (RUNS) {
+    if (by_run) {
+      tile_runs = (uint32_t)kSpecVerThreads / ra.S;
+      tile_step = tile_runs * ra.S;
+    }
+  }
+  for (uint32_t c0 = 0, run0 = 0; c0 < nsc; c0 += tile_step, run0 += tile_runs) {
     const uint32_t c = c0 + (uint32_t)tid;
     uint32_t cnt = 0, i0 = 0, bad = 0, soft = 0;
-    if (c < nsc) {
+    if (c < nsc && (!RUNS || (uint32_t)tid < tile_step)) {
       // The walkers left, per chunk, the last unit-aligned record before the chunk (hand.x: where it takes
       // over; record 0, its arbitrary first byte, if it saw no other) and the last one before the end of the
       // span (hand.y: where the next chunk has to take over), each as index << 16 | position.
@@ -649,7 +796,15 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
     // recorded starts -> block offsets, one wave per chunk of the tile (harmless if the packet fails later:
     // counts of refused chunks are 0, everything is clipped to the packet's own index, and the exact
     // kernels rewrite it)
-    const uint32_t tile_n = min((uint32_t)kSpecVerThreads, nsc - c0);
+    const uint32_t tile_n = min(tile_step, nsc - c0);
+    if constexpr (RUNS) {
+      if (by_run) {
+        spec_ver_emit_runs(s_pos[wv], s_i0, s_base, s_cnt, tile_n, run0, ra.rbase[blockIdx.x], ra, last, out, lane,
+                           (uint32_t)__builtin_amdgcn_readfirstlane(wv));
+        __syncthreads();
+        continue;
+      }
+    }
     // A chunk's block starts are bits in its walker's record, from the hand-over point (at most a macroblock, 384
     // bytes, before the chunk) to the end of the chunk: at most 77 dwords whatever the walker's lead, two per lane.
     // Rank of a bit = starts between the hand-over point and it (popcounts, one wave scan per half); the ranks
@@ -674,18 +829,12 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
         // A plan with runs: the chunk's bits are its run walker's (relative to the run's first byte, as wstart and the
         // hand-over points of the chunk are), or its own row's once k_spec_repair has walked it again.  Of a run walker's
         // bits only those below the end of the chunk are looked at: the ones behind belong to the run's next chunk.
-        // In the first pass nothing has been repaired yet: run and first byte follow from the chunk's number, and the
-        // bits are asked for together with the batch's other loads, not behind them.
+        // (Only the second pass comes here with run walkers' bits: the first emits per run, above.  A launch whose state
+        // names a longer lead had a walker per chunk, which left brow 0.)
         uint32_t br = 0, first_byte = 0;
         if constexpr (RUNS) {
-          if (pass == 1 && run_walkers) {
-            const uint32_t r = (c0 + j) / ra.S;
-            br = ra.rbase[blockIdx.x] + r + 1u;
-            first_byte = r ? r * ra.S * (uint32_t)kSpecChunk - (uint32_t)kSpecLead : 0u;
-          } else {
-            br = ra.brow[R];
-            first_byte = start[u];
-          }
+          br = ra.brow[R];
+          first_byte = start[u];
         }
         const uint32_t* const bits = br ? ra.runbits : recbits;
         const uint32_t wk = br ? br - 1u : R, tiles = br ? spec_run_tiles(ra.S) : (uint32_t)kSpecTilesMax;
