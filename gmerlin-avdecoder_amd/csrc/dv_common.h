@@ -178,4 +178,17 @@ static_assert(Sys625_422::kFrameBytes == 288000 && Sys625_422::kH == 576 && Sys6
 // builds the tables (dv_tables.cpp); false if the code's lengths are not a complete prefix code
 bool build_tables(Tables* t);
 
+// ---- sound (dv_audio_kernels.h) ----
+// Where the samples of a frame's audio DIF blocks go, per line system (0: 525/60, 1: 625/50; the 50 Mbit/s systems have
+// their line system's layout in each channel).  A stereo pair's buffer is a row of 16-bit slots, left and right
+// alternating; sample n of audio block j of DIF sequence q goes to slot shuffle[q][j] + n stride, and a frame carries
+// min_samples[rate] + 0..63 samples a channel (rate 0: 48 kHz, 1: 44.1 kHz, 2: 32 kHz).  What include/mi_dvframe.h's
+// profiles tabulate (lib/dvframe.c:76-104), made from the rule here; tests/test_dv_audio_cpu.py holds the two together.
+struct AudioTables {
+  uint16_t shuffle[2][12][9];  // (525/60 has 10 sequences: its rows 10 and 11 are zero)
+  uint16_t stride[2];
+  uint16_t min_samples[2][3];
+};
+void build_audio_tables(AudioTables* t);
+
 }  // namespace midv

@@ -1,5 +1,6 @@
 // dv_host_systems.h — the five systems as the host layer sees them (one table), the instance, and the decoder's calls:
 // the checks of a resident batch, the decode launch, the one-frame path.  Included by mi_dv.hip; not a kernel header.
+// (The held calls, the encoder and the sound have headers of their own behind this one.)
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
@@ -13,6 +14,7 @@
 #include "dv_decode_kernels.h"
 #include "dv_hold_kernels.h"
 #include "dv_encode_kernels.h"
+#include "dv_audio_kernels.h"
 #include "dv_host_buf.h"
 
 using namespace midv;
@@ -38,6 +40,11 @@ struct Row {
                     unsigned long long*);
   // the launch of k_dv_encode<Sys>
   void (*encode)(hipStream_t, const uint8_t*, unsigned, uint8_t*, const EncTables*, uint32_t, unsigned long long*);
+  // the sound: DIF channels (the stereo pairs of 16-bit sound), the line system (the row of AudioTables), the frame rate
+  // as a fraction, the launches of k_dv_audio_extract<Sys> and k_dv_audio_write<Sys>
+  int chans, line, rate_num, rate_den;
+  void (*audio_extract)(hipStream_t, const uint8_t*, unsigned, uint8_t*, uint32_t, int32_t*, const AudioTables*);
+  void (*audio_write)(hipStream_t, uint8_t*, unsigned, const uint8_t*, uint32_t, uint32_t, const int32_t*, const AudioTables*);
 };
 // a host function of its own: the kernels' S::place stays what dv_common.h makes of it
 template <class S>
@@ -69,11 +76,23 @@ void encode_launch(hipStream_t st, const uint8_t* pics, unsigned n, uint8_t* fra
                    unsigned long long* stats) {
   hipLaunchKernelGGL(k_dv_encode<S>, dim3(kEncGridX<S>, n), dim3(64), 0, st, pics, frames, tab, flags, stats);
 }
+// one workgroup per (pair of the output, frame) / per (channel, frame)
+template <class S>
+void audio_extract_launch(hipStream_t st, const uint8_t* frames, unsigned n, uint8_t* pcm, uint32_t pairs, int32_t* info,
+                          const AudioTables* tab) {
+  hipLaunchKernelGGL(k_dv_audio_extract<S>, dim3(pairs, n), dim3(kAudioThreads), 0, st, frames, pcm, pairs, info, tab);
+}
+template <class S>
+void audio_write_launch(hipStream_t st, uint8_t* frames, unsigned n, const uint8_t* pcm, uint32_t pairs, uint32_t freq,
+                        const int32_t* samples, const AudioTables* tab) {
+  hipLaunchKernelGGL(k_dv_audio_write<S>, dim3((unsigned)S::kChans, n), dim3(kAudioThreads), 0, st, frames, pcm, pairs, freq, samples, tab);
+}
 template <class S>
 constexpr Row row(const char* frames, const char* what, bool says_apt, const char* expected) {
   return {S::kId, S::kFrameBytes, S::kPicBytes, {S::kW, S::kCW, S::kCW}, {S::kH, S::kCH, S::kCH}, S::kChans * S::kSeqs,
           frames, what, expected, says_apt, decode_launch<S>, place_thunk<S>, S::kSegments * 5, rects_thunk<S>, hold_copy_launch<S>,
-          encode_launch<S>};
+          encode_launch<S>, S::kChans, S::kSeqs == 12 ? 1 : 0, S::kSeqs == 12 ? 25 : 30000, S::kSeqs == 12 ? 1 : 1001,
+          audio_extract_launch<S>, audio_write_launch<S>};
 }
 constexpr Row kSystems[] = {
     row<Sys525>("525/60", "525/60 25 Mbit/s DV frame", false, ""),
@@ -115,6 +134,15 @@ struct __attribute__((visibility("hidden"))) mi_dv_ctx {
   DevBuf<EncTables> d_enc;
   DevBuf<unsigned long long> d_enc_stats;
   Timer encode_time{ev_free};  // k_dv_encode (mi_dv_encode_times)
+  // the sound (mi_dv_audio_*): its table; the sample counts of the last written batch on their way to the device
+  struct Audio {
+    explicit Audio(EventPool& pool) : time(pool) {}
+    Timer time;  // k_dv_audio_extract and k_dv_audio_write (mi_dv_audio_times)
+    DevBuf<AudioTables> d_tab;
+    PinnedBuf<int32_t> h_samples;
+    DevBuf<int32_t> d_samples;
+    Event samples_done;  // behind the last upload of h_samples
+  } audio{ev_free};
   // the one-frame paths' buffers, shared by mi_dv_decode_frame*, mi_dv_decode_frame_held and mi_dv_encode_frame: as large
   // as the largest system this instance has seen needs them
   DevBuf<uint8_t> d_frame, d_pic;
@@ -170,6 +198,11 @@ struct BatchCheck {
   int aligned(const void* d_frames, const void* d_pics, const void* d_prev, const char* rule) const {
     if (((uintptr_t)d_frames & 3u) || (((uintptr_t)d_pics | (uintptr_t)d_prev) & 7u))
       return fail(c, MI_DV_ERR_ARG, "%s: d_frames must be %s aligned", who, rule);
+    return MI_DV_OK;
+  }
+  // p on `to` bytes (a power of two)
+  int on(const void* p, unsigned to, const char* name) const {
+    if ((uintptr_t)p & (uintptr_t)(to - 1u)) return fail(c, MI_DV_ERR_ARG, "%s: %s must be %u-byte aligned", who, name, to);
     return MI_DV_OK;
   }
   // `a_bytes` at a and `b_bytes` at b share no byte

@@ -97,6 +97,22 @@ bool build_tables(Tables* t) {
   return true;
 }
 
+// The sound's shuffle from its rule: a sequence's nine audio blocks are three groups of three; block j starts at
+// (j mod 3) * (stride / 3), moved on by (j / 3) * step + 6 * (q mod half) within that third; the sequences of a channel's
+// second half take the slot beside (+ 1: the right sample).  step is 20 of 30 for 525/60, 26 of 36 for 625/50.
+void build_audio_tables(AudioTables* t) {
+  memset(t, 0, sizeof *t);
+  const uint16_t min_samples[2][3] = {{1580, 1452, 1053}, {1896, 1742, 1264}};
+  for (int line = 0; line < 2; line++) {
+    const int seqs = line ? 12 : 10, half = seqs / 2, third = line ? 36 : 30, step = line ? 26 : 20;
+    t->stride[line] = (uint16_t)(3 * third);
+    for (int f = 0; f < 3; f++) t->min_samples[line][f] = min_samples[line][f];
+    for (int q = 0; q < seqs; q++)
+      for (int j = 0; j < 9; j++)
+        t->shuffle[line][q][j] = (uint16_t)((j % 3) * third + ((j / 3) * step + 6 * (q % half)) % third + q / half);
+  }
+}
+
 // the encoder's side of the same code: canonical code words by (run, amplitude), the first (shortest) listing of a pair
 bool build_enc_tables(EncTables* t) {
   memset(t, 0, sizeof *t);

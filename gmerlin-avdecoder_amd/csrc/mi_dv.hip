@@ -1,7 +1,8 @@
 // mi_dv.hip — C ABI (include/mi_dv.h) of the MI355X DV decoder and encoder (25 Mbit/s: 525/60 4:1:1, 625/50 4:2:0, 625/50 4:1:1;
 // 50 Mbit/s: both line systems in 4:2:2).  No CPU path: without a gfx950 device every call fails with a message.
 // The entry points only; what they call: dv_host_buf.h (owned buffers, the timer), dv_host_systems.h (the table of
-// systems, the instance, the decoder), dv_host_hold.h (the held calls), dv_host_encode.h (the encoder).
+// systems, the instance, the decoder), dv_host_hold.h (the held calls), dv_host_encode.h (the encoder),
+// dv_host_audio.h (the sound).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -9,6 +10,7 @@
 #include "dv_host_systems.h"
 #include "dv_host_hold.h"
 #include "dv_host_encode.h"
+#include "dv_host_audio.h"
 
 // header and kernels agree: a system's id, frame, picture and planes as include/mi_dv.h states them
 template <class S, int Id, int FrameBytes, int PicBytes, int H, int CW, int CH>
@@ -71,11 +73,14 @@ mi_dv_ctx* mi_dv_create(int device) {
     fail(nullptr, MI_DV_ERR_ARG, "internal: the variable-length code lists a pair outside the encoder's table");
     return nullptr;
   }
+  AudioTables at;
+  build_audio_tables(&at);
   mi_dv_ctx* c = new mi_dv_ctx();
   c->device = device;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream.p, hipStreamNonBlocking) != hipSuccess ||
       c->d_tab.grow(c, 1, nullptr) != MI_DV_OK || hipMemcpy(c->d_tab, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess ||
       c->d_enc.grow(c, 1, nullptr) != MI_DV_OK || hipMemcpy(c->d_enc, &et, sizeof et, hipMemcpyHostToDevice) != hipSuccess ||
+      c->audio.d_tab.grow(c, 1, nullptr) != MI_DV_OK || hipMemcpy(c->audio.d_tab, &at, sizeof at, hipMemcpyHostToDevice) != hipSuccess ||
       c->d_enc_stats.grow(c, kEncStats, nullptr) != MI_DV_OK ||
       hipMemset(c->d_enc_stats, 0, kEncStats * sizeof(unsigned long long)) != hipSuccess) {
     fail(nullptr, MI_DV_ERR_HIP, "cannot set up device %d: %s", device, hipGetErrorString(hipGetLastError()));
@@ -275,6 +280,39 @@ int mi_dv_encode_stats(mi_dv_ctx* c, long long qno_hist[16], long long* dropped)
   for (int i = 0; i < 16; i++) qno_hist[i] = (long long)v[i];
   *dropped = (long long)v[16];
   return MI_DV_OK;
+}
+
+// ---- the sound ----
+
+int mi_dv_audio_batch(mi_dv_ctx* c, int system, const void* d_frames, int n, void* d_pcm, int pairs, void* d_info) {
+  const Row* r = find(system);
+  if (!r) return fail(c, MI_DV_ERR_ARG, "mi_dv_audio_batch: unknown system %d", system);
+  return audio_batch(c, *r, "mi_dv_audio_batch", d_frames, n, d_pcm, pairs, d_info);
+}
+
+int mi_dv_audio_write_batch(mi_dv_ctx* c, int system, void* d_frames, int n, const void* d_pcm, int pairs, int samplerate,
+                            const int* samples) {
+  const Row* r = find(system);
+  if (!r) return fail(c, MI_DV_ERR_ARG, "mi_dv_audio_write_batch: unknown system %d", system);
+  return audio_write_batch(c, *r, "mi_dv_audio_write_batch", d_frames, n, d_pcm, pairs, samplerate, samples);
+}
+
+int mi_dv_audio_samples(int system, int samplerate, long long frame) {
+  const Row* r = find(system);
+  if (!r || audio_freq(samplerate) < 0 || frame < 0 || frame > (1ll << 31))
+    return fail(nullptr, MI_DV_ERR_ARG, "mi_dv_audio_samples: system %d, %d Hz, frame %lld out of range", system, samplerate, frame);
+  return audio_cadence(*r, samplerate, frame);
+}
+
+int mi_dv_audio_times(mi_dv_ctx* c, float* total_ms, int* launches) {  // k_dv_audio_extract, k_dv_audio_write
+  return times(c, c ? &c->audio.time : nullptr, 1, total_ms, launches);
+}
+
+size_t mi_dv_audio_copy_tables(void* out, size_t cap) {
+  AudioTables t;
+  build_audio_tables(&t);
+  if (out && cap >= sizeof t) memcpy(out, &t, sizeof t);
+  return sizeof t;
 }
 
 }  // extern "C"

@@ -27,7 +27,10 @@ EXPORTS = ["mi_dv_device_count", "mi_dv_create", "mi_dv_destroy", "mi_dv_last_er
            "mi_dv_copy_tables", "mi_dv_system_of", "mi_dv_decode_batch_sys", "mi_dv_decode_frame_sys", "mi_dv_mb_place",
            "mi_dv_profile_of", "mi_dv_kind_of", "mi_dv_mb_rects", "mi_dv_held_macroblocks", "mi_dv_decode_batch_held",
            "mi_dv_hold_stats", "mi_dv_hold_times", "mi_dv_decode_frame_held", "mi_dv_hold_reset", "mi_dv_encode_batch",
-           "mi_dv_encode_frame", "mi_dv_encode_times", "mi_dv_encode_stats"]
+           "mi_dv_encode_frame", "mi_dv_encode_times", "mi_dv_encode_stats", "mi_dv_audio_batch", "mi_dv_audio_write_batch",
+           "mi_dv_audio_samples", "mi_dv_audio_times", "mi_dv_audio_copy_tables"]
+AUDIO_PAIRS, AUDIO_PAIR_BYTES = 4, 8192  # include/mi_dv.h: MI_DV_AUDIO_PAIRS, MI_DV_AUDIO_PAIR_BYTES
+AUDIO_CHANNELS = {SYS_525_60: 1, SYS_625_50: 1, SYS_625_50_411: 1, SYS_525_60_422: 2, SYS_625_50_422: 2}  # DIF channels
 STA_ERRORS = 0x8080  # the default mask of held macroblocks: STA 0111 and 1111 (include/mi_dv.h: MI_DV_STA_ERRORS)
 _LIB = None
 u8p = C.POINTER(C.c_uint8)
@@ -87,6 +90,12 @@ def load():
     L.mi_dv_encode_frame.argtypes = [vp, C.c_int, C.POINTER(u8p), C.POINTER(C.c_int), u8p, C.c_size_t, C.c_int]
     L.mi_dv_encode_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     L.mi_dv_encode_stats.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.mi_dv_audio_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]
+    L.mi_dv_audio_write_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.mi_dv_audio_samples.argtypes = [C.c_int, C.c_int, C.c_longlong]
+    L.mi_dv_audio_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    L.mi_dv_audio_copy_tables.argtypes = [vp, C.c_size_t]
+    L.mi_dv_audio_copy_tables.restype = C.c_size_t
     _LIB = L
     return L
 
@@ -98,6 +107,25 @@ def tables():
     a = np.zeros(n // 4, np.uint32)
     L.mi_dv_copy_tables(a.ctypes.data, n)
     return {"lut9": a[:512], "lut2": a[512:576], "tab": a[576:704].reshape(2, 64), "shift4": a[704:728]}
+
+
+def audio_tables():
+    """the sound's layout table as both audio kernels get it: first-slot shuffle [line system][sequence][audio block],
+    stride and minimum samples (48, 44.1, 32 kHz) per line system (0: 525/60, 1: 625/50) (host-side)"""
+    L = load()
+    n = L.mi_dv_audio_copy_tables(None, 0)
+    a = np.zeros(n // 2, np.uint16)
+    L.mi_dv_audio_copy_tables(a.ctypes.data, n)
+    return {"shuffle": a[:216].reshape(2, 12, 9), "stride": a[216:218], "min_samples": a[218:224].reshape(2, 3)}
+
+
+def audio_samples(system, samplerate, k):
+    """the samples per channel of frame k (from 0) of an unlocked stream of the system at the rate (host-side)"""
+    L = load()
+    n = L.mi_dv_audio_samples(system, samplerate, k)
+    if n < 0:
+        raise MiDvError(L.mi_dv_last_error(None).decode())
+    return n
 
 
 def geometry(system):
@@ -343,6 +371,58 @@ class MiDv:
         hist, dropped = (C.c_longlong * 16)(), C.c_longlong()
         self._chk(self.L.mi_dv_encode_stats(self.c, hist, C.byref(dropped)))
         return np.array(hist[:], np.int64), dropped.value
+
+    # ---- the sound of resident frames (include/mi_dv.h; parity unpinned like the host reader) ----
+    def audio_batch(self, system, d_frames, n, d_pcm, pairs, d_info):
+        """n resident frames -> d_pcm[n][pairs][AUDIO_PAIR_BYTES] (interleaved stereo int16) and d_info[n][4] int32 (samples
+        per channel, rate, pairs carried, bits), queued on the instance's stream"""
+        self._chk(self.L.mi_dv_audio_batch(self.c, system, d_frames, n, d_pcm, pairs, d_info))
+
+    def write_audio_batch(self, system, d_frames, n, d_pcm, pairs, samplerate, samples):
+        """16-bit PCM (the layout audio_batch writes) into the audio blocks of n resident frames; samples: one count per
+        frame, each within the system's window at the rate"""
+        samples = [int(s) for s in samples]
+        if len(samples) != n:
+            raise MiDvError(f"write_audio_batch: {len(samples)} sample counts for {n} frames")
+        self._chk(self.L.mi_dv_audio_write_batch(self.c, system, d_frames, n, d_pcm, pairs, samplerate, (C.c_int * n)(*samples)))
+
+    def extract_audio(self, frames, system, pairs=None):
+        """host frames -> (info, pcm): info an (n, 4) int32 array as audio_batch writes it, pcm[i][k] pair k of frame i as
+        an int16 view of samples x 2 (left, right), trimmed to the frame's samples (none where the frame has no sound).
+        pairs: how many pairs to fetch (default: as many as the system can carry in 12-bit mode)"""
+        fb = geometry(system)[0]
+        frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, fb)
+        n = frames.shape[0]
+        pairs = 2 * AUDIO_CHANNELS[system] if pairs is None else pairs
+        with self._resident(frames, n * max(pairs, 1) * AUDIO_PAIR_BYTES, n * 16) as (df, dp, di):
+            self.audio_batch(system, df, n, dp, pairs, di)
+            self.sync()
+            info = self.d2h(di, n * 16).view(np.int32).reshape(n, 4)
+            raw = self.d2h(dp, n * pairs * AUDIO_PAIR_BYTES).view(np.int16).reshape(n, pairs, AUDIO_PAIR_BYTES // 4, 2)
+        return info, [[raw[i, k, :max(int(info[i, 0]), 0)] for k in range(pairs)] for i in range(n)]
+
+    def write_audio(self, frames, system, pcm, samplerate, samples=None):
+        """host frames with 16-bit sound written into their audio blocks -> host frames.  pcm[i][k]: int16, samples x 2, of
+        pair k of frame i (at least the system's channels; shorter than the frame's samples: silence follows); samples:
+        one count per frame (default: audio_samples(system, samplerate, i))"""
+        fb = geometry(system)[0]
+        frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, fb)
+        n, pairs = frames.shape[0], AUDIO_CHANNELS[system]
+        if samples is None:
+            samples = [audio_samples(system, samplerate, i) for i in range(n)]
+        img = np.zeros((n, pairs, AUDIO_PAIR_BYTES // 2), np.int16)
+        for i in range(n):
+            for k in range(pairs):
+                a = np.ascontiguousarray(pcm[i][k], np.int16).ravel()[:AUDIO_PAIR_BYTES // 2]
+                img[i, k, :a.size] = a
+        with self._resident(frames, img) as (df, dp):
+            self.write_audio_batch(system, df, n, dp, pairs, samplerate, samples)
+            self.sync()
+            return self.d2h(df, n * fb).reshape(n, fb)
+
+    def audio_times(self):
+        """(total milliseconds, launches) of k_dv_audio_extract and k_dv_audio_write since the last call"""
+        return self._times(self.L.mi_dv_audio_times)
 
     def close(self):
         if self.c:

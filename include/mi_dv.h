@@ -76,8 +76,8 @@ int mi_dv_sync(mi_dv_ctx *c);
 int mi_dv_decode_batch(mi_dv_ctx *c, const void *d_frames, int n, void *d_pics);
 /* Device time of k_dv_decode: every mi_dv_decode_batch brackets its launch with HIP events on the instance's stream;
  * this sums them over the launches since the last call (synchronises, then forgets them).  Where nobody asks, the newest
- * 4096 launches are kept and older ones forgotten; so do mi_dv_hold_times and mi_dv_encode_times, each with 4096 of its
- * own. */
+ * 4096 launches are kept and older ones forgotten; so do mi_dv_hold_times, mi_dv_encode_times and mi_dv_audio_times, each
+ * with 4096 of its own. */
 int mi_dv_kernel_times(mi_dv_ctx *c, float *total_ms, int *launches);
 
 /* One frame from host memory into the caller's planes (Y, Cb, Cr) with the caller's strides — what a
@@ -184,7 +184,7 @@ int mi_dv_hold_reset(mi_dv_ctx *c);
  * the oracle.  Nothing here was compared with another DV implementation.  Every frame is complete: the video segments
  * (forward transforms, quantisation by the largest quantisation number at which a segment fits its 2,680 AC bits, the
  * three passes), block ids with the channel bit, DSF, the system's default APT and VAUX stype (mi_dv_kind_of answers the
- * system), zeros everywhere else: no audio, subcode or VAUX content.  flags: bit 0 lets a block take the 2-4-8 transform
+ * system), zeros everywhere else: no subcode or VAUX content, and no audio until mi_dv_audio_write_batch.  flags: bit 0 lets a block take the 2-4-8 transform
  * where its two fields differ, bit 1 gives every block a class by its content (clear: class 0). */
 
 /* n pictures of the system's size, resident in device memory and back to back (the layout mi_dv_decode_batch_sys
@@ -202,6 +202,42 @@ int mi_dv_encode_times(mi_dv_ctx *c, float *total_ms, int *launches);
 /* Of the last encoded batch: the video segments per chosen quantisation number, and the levels the overflow rule
  * dropped (a segment that does not fit at quantisation number 0 loses last levels of its longest blocks).  Synchronises. */
 int mi_dv_encode_stats(mi_dv_ctx *c, long long qno_hist[16], long long *dropped);
+
+/* ---- the sound of resident frames, read and written on the device ----
+ *
+ * What include/mi_dvframe.h's host reader does with one frame, for a batch: the AAUX source pack of every frame (audio
+ * block 3 of sequence 0: samples beyond the rate's minimum, rate, quantisation), then the de-shuffle of its audio blocks
+ * into interleaved stereo PCM, byte for byte what that reader writes into zeroed buffers (the statement: tests/dvaudio.py).
+ * PARITY UNPINNED like the reader.  The other way round only 16-bit sound is written; the AAUX packs it writes are this
+ * repository's reading of IEC 61834-4 (nothing in the reference writes any): this library's readers read them back. */
+enum { MI_DV_AUDIO_PAIRS = 4, MI_DV_AUDIO_PAIR_BYTES = 8192 };
+/* n resident frames of `system` -> d_pcm[n][pairs][MI_DV_AUDIO_PAIR_BYTES] (interleaved stereo S16LE, 16-byte aligned),
+ * d_info[n][4] int32 (4-byte aligned): samples per channel (0: no source pack, -1: unsupported quantisation or rate), and,
+ * where that is positive (else 0): the rate in Hz, the pairs the frame's blocks fill (the system's channels, twice as many
+ * in 12-bit mode), the bits (16 / 12).  Every byte of d_pcm is written: past 4 * samples, and in pairs the frame does not
+ * carry, zero.  pairs 1..4; pairs the frame carries beyond `pairs` are dropped, as the host call drops pairs it has no
+ * buffer for.  Queued on the instance's stream; pair with mi_dv_sync.  MI_DV_ERR_ARG, with nothing launched, for an unknown
+ * system, n out of 1..65535, NULL or misaligned buffers, pairs out of range, buffers that overlap. */
+int mi_dv_audio_batch(mi_dv_ctx *c, int system, const void *d_frames, int n, void *d_pcm, int pairs, void *d_info);
+/* PCM into the audio blocks of n resident frames (16-bit): all 9 audio DIF blocks of every sequence are rewritten whole
+ * (ids as the encoder writes them, AAUX packs, samples) and no other byte.  d_pcm as above; pair k goes to DIF channel k.
+ * samplerate 48000 / 44100 / 32000; samples[i] (host array, read before the call returns) within [min, min + 63] of the
+ * system and rate (525/60: min 1580 / 1452 / 1053, 625/50: 1896 / 1742 / 1264); pairs >= the system's channels (1 or 2),
+ * the first ones are used.  A sample of -32768 is written as -32767 (0x8000 is the format's "no sample").  Queued on the
+ * instance's stream: straight after mi_dv_encode_batch it needs no sync.  MI_DV_ERR_ARG, with nothing launched, as above
+ * and for a bad rate or a sample count outside its window. */
+int mi_dv_audio_write_batch(mi_dv_ctx *c, int system, void *d_frames, int n, const void *d_pcm, int pairs,
+                            int samplerate, const int *samples);
+/* The samples of frame `frame` (from 0) of an unlocked stream: floor((k + 1) rate / fps) - floor(k rate / fps) with the
+ * system's frame rate (30000/1001 or 25) in 64-bit integers.  Host only; MI_DV_ERR_ARG for an unknown system or rate and
+ * a frame below 0 or above 2^31 (the products stay in 64 bits). */
+int mi_dv_audio_samples(int system, int samplerate, long long frame);
+/* Device time of k_dv_audio_extract and k_dv_audio_write (one launch a batch call) since the last call, as
+ * mi_dv_kernel_times, which keeps counting k_dv_decode alone. */
+int mi_dv_audio_times(mi_dv_ctx *c, float *total_ms, int *launches);
+/* The sound's layout table exactly as both kernels read it (csrc/dv_common.h, struct AudioTables: uint16 shuffle[2][12][9],
+ * stride[2], min_samples[2][3]; row 0: 525/60, row 1: 625/50).  Host only, as mi_dv_copy_tables. */
+size_t mi_dv_audio_copy_tables(void *out, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -3,8 +3,10 @@
  *
  * What the reference's lib/dvframe.c does is demultiplexing, not pixel decoding: profile
  * detection, a memcpy of the DIF frame into a video packet, audio PCM de-shuffling and subcode
- * pack extraction.  None of it is data-parallel and none of it runs on the GPU here; it is
- * restated so that the DV rows of the scope table exist next to the RTjpeg path.  DV *pixel*
+ * pack extraction.  For one frame none of it is data-parallel, and this file runs on the host; it is
+ * restated so that the DV rows of the scope table exist next to the RTjpeg path.  For a batch of
+ * frames resident in device memory the audio de-shuffle also runs on the device: mi_dv_audio_batch
+ * of mi_dv.h writes, byte for byte, what mi_dv_extract_audio here writes into zeroed buffers.  DV *pixel*
  * decoding (row D4) is libavcodec's in the reference and is not part of this repository.
  *
  * PARITY UNPINNED: lib/dvframe.c cannot be compiled in the build container (it needs gavl
