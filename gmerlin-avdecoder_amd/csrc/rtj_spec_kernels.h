@@ -12,8 +12,9 @@
 //                  starts there, and runs RTjpeg_s2b's length rule (lib/RTjpeg.c:157-186, 2704) as a
 //                  byte-serial state machine over lead + chunk, recording every block start as ONE BIT per stream
 //                  byte (round 3; 16-bit positions through an LDS ring before).
-//                  64 chunks advance in lockstep per wave: 15 vector instructions per byte for 64
-//                  streams, against ~20 per BLOCK POSITION AND TYPE in k_index_summarize.
+//                  64 chunks advance in lockstep per wave: 12 vector instructions and one LDS read per byte
+//                  for 64 streams (10 and none where all blocks parse alike), against ~20 per BLOCK POSITION AND
+//                  TYPE in k_index_summarize.
 //                  In launches large enough to fill the device without it, one lane per RUN of up to four chunks behind
 //                  ONE lead (SpecRunDev, spec_run_length): the records stay per chunk.
 //   k_spec_verify  per packet: the last (macro)block start a walker saw in its lead, i.e. before its
@@ -159,10 +160,10 @@ template <class Out>
 inline void spec_packet_runs(uint32_t frame, uint32_t chunk0, uint32_t nsc, uint32_t S, Out& out) {
   for (uint32_t c = 0; c < nsc; c += S) out.push_back(SpecRunDev{frame, c, nsc - c < S ? nsc - c : S, chunk0 + c});
 }
-// Which S a plan takes.  The compiled walkers take 94 vector registers where all blocks parse alike and 97 where luma
+// Which S a plan takes.  The compiled walkers take 96 vector registers where all blocks parse alike and 97 where luma
 // and chroma differ (k_spec_walk_any, either kind of plan; .vgpr_count of the code object): allocated in eights out of a
-// SIMD's 512 that is 5 and 4 waves per SIMD, 5,120 and 4,096 resident waves on 256 CUs, and the 5 KB of LDS a wave takes
-// would allow 8.  A GENERATION is counted with the larger figure: 327,680 walker lanes.  All walkers of a launch take the
+// SIMD's 512 that is 5 and 4 waves per SIMD, 5,120 and 4,096 resident waves on 256 CUs, and the 5 KB (6.5 KB with the
+// phase table) of LDS a wave takes would allow 8 (6).  A GENERATION is counted with the larger figure: 327,680 walker lanes.  All walkers of a launch take the
 // same number of byte steps, so the last, partly filled generation is lost time, up to 1 / generations of the launch,
 // and a run of S chunks makes S times fewer, S times longer walkers.  A plan takes the longest run that still leaves
 // kSpecRunMinGens full generations, and one walker per chunk under 2 * kSpecRunMinGens generations, as before.  The
@@ -207,18 +208,29 @@ constexpr int kSpecVerWindow = 512;  // ranks a wave of k_spec_verify orders in 
 constexpr int kSpecVerBatch = MIRTJ_SPEC_VER_BATCH;  // chunks whose records a wave of k_spec_verify copies side by side
 constexpr int kSpecVerThreads = MIRTJ_SPEC_VER_THREADS;  // k_spec_verify: chunks of a packet handled side by side  // grid rows of the exact kernels when they only serve refused packets
 
-// One byte of the walker's state machine, spelled out: 15 vector instructions (the compiler's version of the same C++
-// had 21-22: it keeps lane masks as 0/1 integers and splits the counters; round 2's, with 16-bit records, 17 and an LDS
-// write).  State: u = units of the current block so far, q = 5 - (block number within the macroblock), rb = DC + raw
-// bytes of the current block's type, em = lane mask "the previous byte ended a block" = "a block starts at this byte",
-// bits = the start bits of the 32 bytes in hand (shifted in with one add-with-carry).  The byte's token value t = byte - 63
-// and max(1, t) arrive precomputed (tm, wtm) and the macro computes them for the NEXT byte (byte NSEL of word wn): that
-// is independent work to put into the two wait states gfx950 wants between a vector compare that writes a lane mask
-// and a vector instruction that reads it (the assembler pads nothing inside an asm statement).  Checked gaps: vcc (a) ->
-// s_and: b, c; ma (b) -> g: c .. f; em (i) -> l: j + s_nop; mx (m) -> p: n, o; my (n) -> q: o, p.
+// One byte of the walker's state machine, spelled out: 12 vector instructions and one LDS read (the compiler's version
+// of the same C++ had 21-22: it keeps lane masks as 0/1 integers and splits the counters; round 2's, with 16-bit
+// records, 17 and an LDS write; with the macroblock phase in registers — a counter, two compares and two selects on
+// every byte for values that change once per block, ~12 bytes — 15).  State: u = units of the current block so far,
+// em = lane mask "the previous byte ended a block" = "a block starts at this byte", bits = the start bits of the 32
+// bytes in hand (shifted in with one add-with-carry), and the PHASE: which block of the macroblock this is and how many
+// DC + raw bytes its type has.  The phase lives in a table of six entries per lane in LDS (spec_phase_entry, below:
+// byte 0 = rb, byte 1 = the block's number, bits 16-31 = the LDS address of the next block's entry; the last entry
+// points to the first); the lane holds the current entry in cu and the address it names in pt.  Every step reads the
+// next entry from pt first and takes it at the end if the byte ended a block: the read has the whole step, and the
+// three other waves of the SIMD, to come back, and is consumed inside the same statement (what a statement loads the
+// compiler does not count: nothing of it may be pending when the statement ends).  The raw-byte compare (b) takes rb
+// out of cu with a byte select.  tools/ubench/spec_phase_step.hip runs this step against the one before it
+// (profiles/spec_phase_table/ubench.txt: 45 against 57 cycles per byte and wave, the same bits).
+// The byte's token value t = byte - 63 and max(1, t) arrive precomputed (tm, wtm) and the macro computes them for the
+// NEXT byte (byte NSEL of word wn): that is independent work to put into the two wait states gfx950 wants between a
+// vector compare that writes a lane mask and a vector instruction that reads it (the assembler pads nothing inside an
+// asm statement).  Checked gaps: vcc (a) -> s_and: b, c; ma (b) -> g: c .. f; em (i) -> o: j + s_waitcnt + s_nop.
+// The s_and writes SCC, which the statement says: a loop compare the compiler had placed ahead of the steps would be lost.
 #define MIRTJ_SPEC_STEP(NSEL)                                                                                     \
-  asm("v_cmp_eq_i32_e32 vcc, %[kn64], %[tm]\n\t"        /* a: the byte is 0xFF */                                  \
-      "v_cmp_lt_i32_e64 %[ma], %[u], %[rb]\n\t"         /* b: a DC or raw byte */                                  \
+  asm("ds_read_b32 %[nx], %[pt]\n\t"                   /* the next block's entry, wanted at r */                  \
+      "v_cmp_eq_i32_e32 vcc, %[kn64], %[tm]\n\t"        /* a: the byte is 0xFF */                                  \
+      "v_cmp_lt_i32_sdwa %[ma], %[u], %[cu] src0_sel:DWORD src1_sel:BYTE_0\n\t" /* b: a DC or raw byte */          \
       "v_addc_co_u32_e64 %[bits], %[mz], %[bits], %[bits], %[em]\n\t" /* c: bits = bits << 1 | starts-here */     \
       "s_and_b64 vcc, vcc, %[em]\n\t"                   /* 0xFF as a block's first byte: one-byte block */        \
       "v_sub_u32_sdwa %[tn], sext(%[wn]), %[k63] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:" NSEL             \
@@ -228,17 +240,25 @@ constexpr int kSpecVerThreads = MIRTJ_SPEC_VER_THREADS;  // k_spec_verify: chunk
       "v_add_u32_e32 %[u], %[u], %[wt]\n\t"             /* h */                                                    \
       "v_cmp_lt_i32_e64 %[em], 63, %[u]\n\t"            /* i: 64 units: the block ends with this byte */           \
       "v_max_i32_e32 %[wtn], 1, %[tn]\n\t"              /* j: the next byte's token weight */                     \
+      "s_waitcnt lgkmcnt(0)\n\t"                        /* nx is there */                                          \
       "s_nop 0\n\t"                                                                                                \
-      "v_subb_co_u32_e64 %[q], vcc, %[q], 0, %[em]\n\t" /* l */                                                    \
-      "v_cmp_lt_i32_e64 %[mx], %[q], 0\n\t"             /* m: past the macroblock's last block */                  \
-      "v_cmp_lt_u32_e64 %[my], %[q], 2\n\t"             /* n: a chroma block is next */                            \
       "v_cndmask_b32_e64 %[u], %[u], 0, %[em]\n\t"      /* o */                                                    \
-      "v_cndmask_b32_e64 %[q], %[q], 5, %[mx]\n\t"      /* p */                                                    \
-      "v_cndmask_b32_e64 %[rb], %[lb], %[cb], %[my]"    /* q */                                                    \
-      : [u] "+v"(u), [q] "+v"(q), [rb] "+v"(rb), [em] "+s"(em), [bits] "+v"(bits_), [tn] "=&v"(tn_), [wtn] "=&v"(wtn_), \
-        [wt] "=&v"(wt_), [wr] "=&v"(wr_), [ma] "=&s"(ma_), [mx] "=&s"(mx_), [my] "=&s"(my_), [mz] "=&s"(mz_)         \
-      : [tm] "v"(tm_), [wtm] "v"(wtm_), [wn] "v"(wn_), [k63] "v"(k63), [kn64] "v"(kn64), [lb] "v"(lb), [cb] "v"(cb)  \
-      : "vcc")
+      "v_cndmask_b32_e64 %[cu], %[cu], %[nx], %[em]\n\t" /* r: on to the next block of the macroblock */          \
+      "v_lshrrev_b32_e32 %[pt], 16, %[cu]"              /* s: where the entry after it is */                       \
+      : [u] "+v"(u), [cu] "+v"(cu), [pt] "+v"(pt), [em] "+s"(em), [bits] "+v"(bits_), [tn] "=&v"(tn_),             \
+        [wtn] "=&v"(wtn_), [wt] "=&v"(wt_), [wr] "=&v"(wr_), [nx] "=&v"(nx_), [ma] "=&s"(ma_), [mz] "=&s"(mz_)     \
+      : [tm] "v"(tm_), [wtm] "v"(wtm_), [wn] "v"(wn_), [k63] "v"(k63), [kn64] "v"(kn64)                            \
+      : "vcc", "scc")
+
+// The phase table: [entry][lane] dwords, so that the 64 lanes of a read hit 64 different dwords of one 256-byte row
+// (conflict-free).  Per lane, because the lanes of a wave can belong to packets of different qualities.
+constexpr int kSpecPhases = 6;  // blocks of a macroblock
+constexpr int kSpecPhaseWords = kSpecPhases * 64;
+static_assert(64 * kSpecRingRow + kSpecPhaseWords * 4 < 8192, "a walker wave's LDS: ring and phase table under 8 KB");
+// entry p of the lane whose entry 0 is at LDS address `tab0` (below 64 KB: the address field is 16 bits)
+__host__ __device__ constexpr uint32_t spec_phase_entry(uint32_t tab0, int p, int lb, int cb) {
+  return ((tab0 + (uint32_t)((p + 1) % kSpecPhases) * 256u) << 16) | ((uint32_t)p << 8) | (uint32_t)(p < 4 ? lb : cb);
+}
 
 // The same when every packet of the launch has lb8 == cb8 (two thirds of the qualities): all blocks parse
 // alike, no phase to track, 10 vector instructions.
@@ -275,7 +295,8 @@ struct SpecReset {
 // to the RUN's first byte: at every chunk boundary inside the run, the pair it records today at its chunk's start and
 // end.  The proof (k_spec_verify) keeps its unit; a boundary inside a run holds by construction.
 template <bool PHASE, int LEAD, bool RUNS = false>
-__device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, const FrameDev* __restrict__ frames,
+__device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, uint32_t* __restrict__ s_phase,
+                                               const FrameDev* __restrict__ frames,
                                                const SpecChunkDev* __restrict__ chunks, uint32_t total,
                                                const uint8_t* __restrict__ stream, const QTab* __restrict__ lut,
                                                uint32_t* __restrict__ recbits, uint32_t* __restrict__ nrec,
@@ -368,9 +389,21 @@ __device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, con
 
   // ---- the length rule as a branch-free state machine.  A block is complete after 64 units: DC and the
   //      raw bytes count 1 each, a token its weight.  u = units of the current block so far, rb = its
-  //      1 + bt8 DC/raw bytes, q = 5 - its number within the macroblock ----
-  int u = 0, rb = lb;
-  uint32_t q = 5;        // 5 - block number within the macroblock
+  //      1 + bt8 DC/raw bytes (PHASE: byte 0 of cu, the lane's current entry of the phase table, whose byte 1 is the
+  //      block's number within the macroblock; pt = the LDS address of the entry after it) ----
+  int u = 0;
+  [[maybe_unused]] const int rb = lb;
+  uint32_t cu = 0, pt = 0;
+  if constexpr (PHASE) {
+    // the lane's six entries, written once: the steps read them inside asm statements, which the compiler cannot see,
+    // so the writes are pinned in front of them (LDS serves a wave's accesses in order)
+    const uint32_t tab0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)s_phase + 4u * (uint32_t)lane;
+#pragma unroll
+    for (int p = 0; p < kSpecPhases; p++) s_phase[p * 64 + lane] = spec_phase_entry(tab0, p, lb, cb);
+    asm volatile("" ::"v"(tab0) : "memory");
+    cu = spec_phase_entry(tab0, 0, lb, cb);
+    pt = cu >> 16;
+  }
   uint64_t em = ~0ull;   // the walker's first byte is taken to be a macroblock's first
   // idle lanes of the last wave own the spare walker after the last one
   const uint32_t gw = act ? g : total;
@@ -380,13 +413,13 @@ __device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, con
 
   // (index << 16 | position) of the last unit-aligned block start below the start of tile `lt` (walker-relative; the
   // unit is the macroblock, or the block when lb8 == cb8: k_spec_verify).  Called between tiles: cnt counts the starts
-  // below the limit, the current block has number 5 - q in its macroblock, and if the byte before the limit ended a
+  // below the limit, the current block has number (cu >> 8) & 255 in its macroblock, and if the byte before the limit ended a
   // block (the lane's bit of em), a start AT the limit is pending that is in neither.  The unit start wanted is at
   // most a macroblock (384 bytes) back: inside the four tiles the ring holds.
   const bool by_block = lb == cb;
   auto last_aligned_below = [&](int lt) -> uint32_t {
     const int d = (int)((em >> lane) & 1ull);
-    int r = by_block ? 0 : 5 - (int)q - d;  // starts between the one wanted and the limit
+    int r = by_block ? 0 : (int)((cu >> 8) & 255u) - d;  // starts between the one wanted and the limit
     r = r < 0 ? r + 6 : r;
     int left = r;
     for (int back = 1; back <= 4 && back <= lt; back++) {
@@ -478,8 +511,9 @@ __device__ __forceinline__ void spec_walk_body(uint8_t* __restrict__ s_ring, con
       for (int b = 0; b < 16; b++) {
         const uint32_t wn_ = wd[(b + 1) >> 2];
         int tn_, wtn_, wt_, wr_;
-        uint64_t ma_, mx_, my_, mz_;
-        if (PHASE) {
+        [[maybe_unused]] uint32_t nx_;
+        uint64_t ma_, mz_;
+        if constexpr (PHASE) {
           switch ((b + 1) & 3) {
             case 0: MIRTJ_SPEC_STEP("BYTE_0"); break;
             case 1: MIRTJ_SPEC_STEP("BYTE_1"); break;
@@ -530,7 +564,8 @@ __global__ __launch_bounds__(64) void k_spec_walk(const FrameDev* __restrict__ f
                                                    uint32_t* __restrict__ nrec, uint32_t* __restrict__ wstart,
                                                    uint2* __restrict__ hand, const SpecReset rs, const SpecRunArgs ra) {
   __shared__ __attribute__((aligned(16))) uint8_t s_ring[64 * kSpecRingRow];
-  spec_walk_body<PHASE, LEAD, RUNS>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
+  __shared__ uint32_t s_phase[PHASE ? kSpecPhaseWords : 1];
+  spec_walk_body<PHASE, LEAD, RUNS>(s_ring, s_phase, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
 }
 
 // The form the plan's policy state names (none while the speculation is paused, k_spec_policy): ONE dispatch whatever
@@ -547,14 +582,15 @@ __global__ __launch_bounds__(64) void k_spec_walk_any(const FrameDev* __restrict
                                                        uint2* __restrict__ hand, const SpecReset rs, const SpecRunArgs ra,
                                                        const uint32_t* __restrict__ state) {
   __shared__ __attribute__((aligned(16))) uint8_t s_ring[64 * kSpecRingRow];
+  __shared__ uint32_t s_phase[PHASE ? kSpecPhaseWords : 1];
   if (state[kSpecStPause]) return;
   const uint32_t level = state[kSpecStLong];  // wave-uniform
   if (level == 0u)
-    spec_walk_body<PHASE, kSpecLead, RUNS>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
+    spec_walk_body<PHASE, kSpecLead, RUNS>(s_ring, s_phase, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
   else if (level == 1u)
-    spec_walk_body<PHASE, kSpecLeadLong>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
+    spec_walk_body<PHASE, kSpecLeadLong>(s_ring, s_phase, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
   else
-    spec_walk_body<PHASE, kSpecLeadVery>(s_ring, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
+    spec_walk_body<PHASE, kSpecLeadVery>(s_ring, s_phase, frames, chunks, total, stream, lut, recbits, nrec, wstart, hand, rs, ra);
 }
 
 // ---- k_spec_verify's emission where the launch's walkers walked runs: the RUN is the unit ----
