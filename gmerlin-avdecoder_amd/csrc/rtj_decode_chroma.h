@@ -13,7 +13,8 @@
 //   2. the busy blocks (about 3 x 17) are compacted over the lanes: block of rank k hands its first eight stream
 //      bytes to lane k through the LDS; lanes 0 .. n-1 parse and transform them with the short forms of the
 //      transform (transform_lo: the three- and four-input butterflies) and put the pixel rows back into the LDS;
-//   3. the home lanes of each group store their rows — DC-only ones from a register, busy ones from the LDS — as the
+//   3. the home lanes of each group store their rows — read back from the LDS two rows at a time, busy ones the rows
+//      of their rank, DC-only ones 16 bytes of their pixel out of their own scratch — as the
 //      same whole 256-byte row segments (32 blocks of Cb, 32 of Cr) a plain round stores.  (Round 2 deferred the
 //      busy blocks to a second kernel and lost on partial-line writes; nothing is deferred here.)
 // A group with a block the short forms do not cover (longer than eight bytes, a coefficient outside the low 4x4, bytes
@@ -49,6 +50,8 @@ __device__ unsigned long long g_pool_stamps[16];
 
 typedef uint32_t mirtj_u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t mirtj_u32x3 __attribute__((ext_vector_type(3)));
+typedef uint32_t mirtj_u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) mirtj_u32x4 lds_u32x4_t;
 
 __device__ __forceinline__ void chroma_pool_wave(uint32_t* __restrict__ s_lds, const FrameDev* __restrict__ frames,
                                                  const uint32_t fidx, const uint32_t slot, const uint32_t slots,
@@ -336,23 +339,33 @@ __device__ __forceinline__ void chroma_pool_wave(uint32_t* __restrict__ s_lds, c
             }
             const uint32_t o = (kblk == 5u ? (uint32_t)(ysz >> 2) : 0u) + 8u * my_ * stride + 8u * mx;
             uint8_t* plane = plane0;  // wave-uniform; steps from row to row on the scalar side
-            const uint32_t fill = (info[q] & 0xFFu) * 0x01010101u;
-            uint32_t ra = lds0 + (info[q] >> 10) * (uint32_t)(kCoefStride * 2);
+            const uint32_t fill = __builtin_amdgcn_perm(info[q], info[q], 0u);  // the pixel (byte 0) in all four bytes
+            // Two rows per 16-byte LDS read, and no choice between `fill` and the LDS row per row: every lane puts 16
+            // bytes of its pixel into its own scratch behind the rows (bytes 64..79: coefficients once, nobody's since
+            // the transform, zeroed again by the next parse), a DC-only lane reads those four times over (step 0), a
+            // busy one the rows of its rank (step 16).  One block without branches: the eight stores below are the
+            // only ones of the group, whatever the mix of classes in the wave.
+            const bool busy = cls == 2u;
+            const mirtj_u32x4 f4 = {fill, fill, fill, fill};
+            *(lds_u32x4_t*)(uintptr_t)(my_a + 64u) = f4;
+            const uint32_t ra = busy ? lds0 + (info[q] >> 10) * (uint32_t)(kCoefStride * 2) : my_a + 64u;
+            const uint32_t rstep = busy ? 16u : 0u;
+            static_assert(kRowStores == 8, "four pairs of rows");
 #pragma unroll
-            for (int r = 0; r < kRowStores; r++) {
+            for (int r = 0; r < kRowStores; r += 2) {
+              const mirtj_u32x4 v = *(const lds_u32x4_t*)(uintptr_t)(ra + (uint32_t)(r >> 1) * rstep);
               mirtj_u32x2 ov;
-              ov.x = fill;
-              ov.y = fill;
-              if (cls == 2u) {
-                ov.x = *(const lds_u32_t*)(uintptr_t)ra;
-                ov.y = *(const lds_u32_t*)(uintptr_t)(ra + 4u);
-              }
               // plain stores: as nontemporal ones these 8-byte-per-lane rows reached memory as 22.8 GB per launch for
               // 17.1 GB of chroma planes (WRITE_SIZE; whatever the row alignment), plain ones as 17.2; the time is the
               // same (profiles/r04/chroma_store_traffic.txt)
+              ov.x = v.x;
+              ov.y = v.y;
               *(mirtj_u32x2*)(plane + o) = ov;
               plane += stride;
-              ra += 8u;
+              ov.x = v.z;
+              ov.y = v.w;
+              *(mirtj_u32x2*)(plane + o) = ov;
+              plane += stride;
             }
           }
         }

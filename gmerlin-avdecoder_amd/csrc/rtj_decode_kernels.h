@@ -805,7 +805,21 @@ __device__ __forceinline__ void decode_wave(uint32_t* __restrict__ s_lds, const 
     r.kblk = r.part == 2u ? 4u + (uint32_t)(lane >> 5) : 2u * r.part + (uint32_t)(lane & 1);
     r.mb = r.grp * (uint32_t)kMbPerGroup + r.dmb;
     r.valid = (kSuper || g < (uint32_t)kDecIters) && r.grp < ngroups && r.mb < f.nmb;  // (kSuper: as many groups as the wave's share has)
+    if constexpr (kSuper) {
+      // the same, with the group's share of the test on the scalar side: the macroblocks the picture has left from the
+      // group's first one on (a group below ngroups starts below nmb), against the lane's place in the group
+      const uint32_t left = r.grp < ngroups ? f.nmb - r.grp * (uint32_t)kMbPerGroup : 0u;  // wave-uniform
+      r.valid = r.dmb < left;
+    }
     return r;
+  };
+  // index into `off` of the block of `s`: 6 * mb + kblk.  kSuper (luma parts only: kblk = 2 * part + (lane & 1),
+  // dmb = lane >> 1): the group's and the part's share is wave-uniform and the lane's a constant, so that the sum costs
+  // an addition per use where the product cost a 32-bit multiplication (a quarter-rate instruction) and three more
+  auto index_of = [&](const Src& s) -> uint32_t {
+    if constexpr (kSuper)
+      return (s.grp * (uint32_t)(6 * kMbPerGroup) + 2u * s.part) + (6u * (uint32_t)(lane >> 1) + (uint32_t)(lane & 1));
+    return 6u * s.mb + s.kblk;
   };
   auto more_after = [&](uint32_t it) -> bool {  // wave-uniform: is there an iteration it + 1
     const uint32_t g = rot ? (it + 1u) / (uint32_t)kParts : it + 1u;
@@ -868,6 +882,22 @@ __device__ __forceinline__ void decode_wave(uint32_t* __restrict__ s_lds, const 
     uint32_t mx, my_;
     const uint32_t mbw = f.mbw, mb0 = grp * (uint32_t)kMbPerGroup;
     const uint32_t gy = mb0 / mbw, gx = mb0 - gy * mbw;  // uniform in k_decode
+    if constexpr (kSuper) {
+      // luma parts only (kblk >> 1 is the part, wave-uniform).  Rows at least a group wide: what the group and the part
+      // decide is added up on the scalar side, the lane's share is a constant, and a lane on the next macroblock row
+      // (dmb >= mbw - gx) adds the step to it: one test and one selection per lane.  (Modulo 2^32 like every offset
+      // here; the sum is the block's offset, below 2^32.)
+      if (mbw >= (uint32_t)kMbPerGroup) {
+        uint32_t st = stride;
+        asm volatile("" : "+s"(st));  // (worked out where it is used: held across the loop it is one more spilled scalar)
+        const uint32_t base = (16u * gy + 8u * (kblk >> 1)) * stride + 16u * gx;  // wave-uniform
+        const uint32_t wrap_step = 16u * (st - mbw);                              // wave-uniform
+        return base + (16u * dmb + 8u * (kblk & 1u)) + (dmb >= mbw - gx ? wrap_step : 0u);
+      }
+      my_ = mb / mbw;
+      mx = mb - my_ * mbw;
+      return (16u * my_ + 8u * (kblk >> 1)) * stride + 16u * mx + 8u * (kblk & 1u);
+    }
     if (mbw >= (uint32_t)kMbPerGroup) {
       const bool wrap = gx + dmb >= mbw;
       mx = wrap ? gx + dmb - mbw : gx + dmb;
@@ -884,8 +914,8 @@ __device__ __forceinline__ void decode_wave(uint32_t* __restrict__ s_lds, const 
   // instead of being carried from iteration to iteration in vector registers: the register count decides how many
   // waves a SIMD holds)
   const Src s0 = source(0u), s1 = source(1u);
-  uint32_t pos0 = off[s0.valid ? 6u * s0.mb + s0.kblk : 0u];  // block start relative to the first data byte
-  uint32_t pos_n = off[s1.valid ? 6u * s1.mb + s1.kblk : 0u];  // the same for the wave's next iteration
+  uint32_t pos0 = off[s0.valid ? index_of(s0) : 0u];  // block start relative to the first data byte
+  uint32_t pos_n = off[s1.valid ? index_of(s1) : 0u];  // the same for the wave's next iteration
   pos0 = s0.valid ? pos0 : 0u;
   bool inside = !kForceGenericPaths && __all(pos0 + kFetchSpan <= f.data_len);  // wave-uniform
   Bytes cur = fetch(pos0, inside, 9);  // 32 bytes (+ alignment): all of most blocks
@@ -1035,7 +1065,7 @@ __device__ __forceinline__ void decode_wave(uint32_t* __restrict__ s_lds, const 
       const Src s2 = source(it + 2u);
       // addresses as a wave-uniform base (scalar registers) plus a 32-bit byte offset per lane: no 64-bit vector
       // arithmetic (a packet is shorter than 2^32 bytes; the index of a packet has fewer than 2^30 entries)
-      const uint32_t offp = s2.valid ? 4u * (6u * s2.mb + s2.kblk) : 0u;
+      const uint32_t offp = s2.valid ? 4u * index_of(s2) : 0u;
       const uint8_t* g4b = data - ((uintptr_t)data & 3u);  // uniform
       uint32_t g4o = (pos_n + (uint32_t)((uintptr_t)data & 3u)) & ~3u;
       // near the packet's end (rare) the bytes are fetched with masks, behind the wait at the end of this iteration —
