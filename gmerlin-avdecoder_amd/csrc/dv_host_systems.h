@@ -1,6 +1,6 @@
 // dv_host_systems.h — the five systems as the host layer sees them (one table), the instance, and the decoder's calls:
 // the checks of a resident batch, the decode launch, the one-frame path.  Included by mi_dv.hip; not a kernel header.
-// (The held calls, the encoder and the sound have headers of their own behind this one.)
+// (The held calls, the encoder, the sound and the timecode have headers of their own behind this one.)
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
@@ -15,6 +15,7 @@
 #include "dv_hold_kernels.h"
 #include "dv_encode_kernels.h"
 #include "dv_audio_kernels.h"
+#include "dv_meta_kernels.h"
 #include "dv_host_buf.h"
 
 using namespace midv;
@@ -45,6 +46,9 @@ struct Row {
   int chans, line, rate_num, rate_den;
   void (*audio_extract)(hipStream_t, const uint8_t*, unsigned, uint8_t*, uint32_t, int32_t*, const AudioTables*);
   void (*audio_write)(hipStream_t, uint8_t*, unsigned, const uint8_t*, uint32_t, uint32_t, const int32_t*, const AudioTables*);
+  // timecode, recording date and time, aspect: the launches of k_dv_meta_extract<Sys> and k_dv_meta_write<Sys>
+  void (*meta_extract)(hipStream_t, const uint8_t*, unsigned, int32_t*);
+  void (*meta_write)(hipStream_t, uint8_t*, unsigned, unsigned long long, uint32_t, long long, uint32_t);
 };
 // a host function of its own: the kernels' S::place stays what dv_common.h makes of it
 template <class S>
@@ -87,12 +91,23 @@ void audio_write_launch(hipStream_t st, uint8_t* frames, unsigned n, const uint8
                         const int32_t* samples, const AudioTables* tab) {
   hipLaunchKernelGGL(k_dv_audio_write<S>, dim3((unsigned)S::kChans, n), dim3(kAudioThreads), 0, st, frames, pcm, pairs, freq, samples, tab);
 }
+// one wave per frame, kMetaExtractWaves of them a workgroup (the last may be partly idle) / one workgroup per frame
+template <class S>
+void meta_extract_launch(hipStream_t st, const uint8_t* frames, unsigned n, int32_t* meta) {
+  hipLaunchKernelGGL(k_dv_meta_extract<S>, dim3((n + kMetaExtractWaves - 1u) / kMetaExtractWaves), dim3(64 * kMetaExtractWaves), 0, st,
+                     frames, (uint32_t)n, meta);
+}
+template <class S>
+void meta_write_launch(hipStream_t st, uint8_t* frames, unsigned n, unsigned long long first_frame, uint32_t drop,
+                       long long rec_seconds, uint32_t wide) {
+  hipLaunchKernelGGL(k_dv_meta_write<S>, dim3(n), dim3(kMetaWriteThreads), 0, st, frames, first_frame, drop, rec_seconds, wide);
+}
 template <class S>
 constexpr Row row(const char* frames, const char* what, bool says_apt, const char* expected) {
   return {S::kId, S::kFrameBytes, S::kPicBytes, {S::kW, S::kCW, S::kCW}, {S::kH, S::kCH, S::kCH}, S::kChans * S::kSeqs,
           frames, what, expected, says_apt, decode_launch<S>, place_thunk<S>, S::kSegments * 5, rects_thunk<S>, hold_copy_launch<S>,
           encode_launch<S>, S::kChans, S::kSeqs == 12 ? 1 : 0, S::kSeqs == 12 ? 25 : 30000, S::kSeqs == 12 ? 1 : 1001,
-          audio_extract_launch<S>, audio_write_launch<S>};
+          audio_extract_launch<S>, audio_write_launch<S>, meta_extract_launch<S>, meta_write_launch<S>};
 }
 constexpr Row kSystems[] = {
     row<Sys525>("525/60", "525/60 25 Mbit/s DV frame", false, ""),
@@ -143,6 +158,11 @@ struct __attribute__((visibility("hidden"))) mi_dv_ctx {
     DevBuf<int32_t> d_samples;
     Event samples_done;  // behind the last upload of h_samples
   } audio{ev_free};
+  // timecode, recording date and time, aspect (mi_dv_meta_*)
+  struct Meta {
+    explicit Meta(EventPool& pool) : time(pool) {}
+    Timer time;  // k_dv_meta_extract and k_dv_meta_write (mi_dv_meta_times)
+  } meta{ev_free};
   // the one-frame paths' buffers, shared by mi_dv_decode_frame*, mi_dv_decode_frame_held and mi_dv_encode_frame: as large
   // as the largest system this instance has seen needs them
   DevBuf<uint8_t> d_frame, d_pic;
@@ -301,7 +321,7 @@ int decode_one(mi_dv_ctx* c, const Row& r, const char* who, const uint8_t* frame
   return planes_out(c, r, c->d_pic, planes, strides);
 }
 
-// the body of the three mi_dv_*_times: waits for the stream, then the timer's sum and `per_pair` launches a pair
+// the body of the mi_dv_*_times: waits for the stream, then the timer's sum and `per_pair` launches a pair
 int times(mi_dv_ctx* c, Timer* t, int per_pair, float* total_ms, int* launches) {
   if (!c || !total_ms || !launches) return MI_DV_ERR_ARG;
   DVCHK(c, hipSetDevice(c->device));

@@ -2,7 +2,7 @@
 // 50 Mbit/s: both line systems in 4:2:2).  No CPU path: without a gfx950 device every call fails with a message.
 // The entry points only; what they call: dv_host_buf.h (owned buffers, the timer), dv_host_systems.h (the table of
 // systems, the instance, the decoder), dv_host_hold.h (the held calls), dv_host_encode.h (the encoder),
-// dv_host_audio.h (the sound).
+// dv_host_audio.h (the sound), dv_host_meta.h (timecode, recording date and time, aspect).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -11,6 +11,7 @@
 #include "dv_host_hold.h"
 #include "dv_host_encode.h"
 #include "dv_host_audio.h"
+#include "dv_host_meta.h"
 
 // header and kernels agree: a system's id, frame, picture and planes as include/mi_dv.h states them
 template <class S, int Id, int FrameBytes, int PicBytes, int H, int CW, int CH>
@@ -313,6 +314,37 @@ size_t mi_dv_audio_copy_tables(void* out, size_t cap) {
   build_audio_tables(&t);
   if (out && cap >= sizeof t) memcpy(out, &t, sizeof t);
   return sizeof t;
+}
+
+// ---- timecode, recording date and time, aspect ----
+
+int mi_dv_meta_batch(mi_dv_ctx* c, int system, const void* d_frames, int n, void* d_meta) {
+  const Row* r = find(system);
+  if (!r) return fail(c, MI_DV_ERR_ARG, "mi_dv_meta_batch: unknown system %d", system);
+  return meta_batch(c, *r, "mi_dv_meta_batch", d_frames, n, d_meta);
+}
+
+int mi_dv_meta_write_batch(mi_dv_ctx* c, int system, void* d_frames, int n, long long first_frame, int drop_frame,
+                           long long rec_seconds, int wide) {
+  const Row* r = find(system);
+  if (!r) return fail(c, MI_DV_ERR_ARG, "mi_dv_meta_write_batch: unknown system %d", system);
+  return meta_write_batch(c, *r, "mi_dv_meta_write_batch", d_frames, n, first_frame, drop_frame, rec_seconds, wide);
+}
+
+int mi_dv_timecode_of(int system, long long frame, int drop_frame, int hmsf[4]) {
+  const Row* r = find(system);
+  if (!r || !hmsf || frame < 0)
+    return fail(nullptr, MI_DV_ERR_ARG, "mi_dv_timecode_of: system %d, frame %lld out of range", system, frame);
+  const int rc = meta_check_drop(nullptr, *r, "mi_dv_timecode_of", drop_frame);
+  if (rc != MI_DV_OK) return rc;
+  uint32_t v[4];
+  meta_timecode(r->line ? 25u : 30u, (uint32_t)drop_frame, (unsigned long long)frame, v);
+  for (int i = 0; i < 4; i++) hmsf[i] = (int)v[i];
+  return MI_DV_OK;
+}
+
+int mi_dv_meta_times(mi_dv_ctx* c, float* total_ms, int* launches) {  // k_dv_meta_extract, k_dv_meta_write
+  return times(c, c ? &c->meta.time : nullptr, 1, total_ms, launches);
 }
 
 }  // extern "C"

@@ -28,7 +28,10 @@ EXPORTS = ["mi_dv_device_count", "mi_dv_create", "mi_dv_destroy", "mi_dv_last_er
            "mi_dv_profile_of", "mi_dv_kind_of", "mi_dv_mb_rects", "mi_dv_held_macroblocks", "mi_dv_decode_batch_held",
            "mi_dv_hold_stats", "mi_dv_hold_times", "mi_dv_decode_frame_held", "mi_dv_hold_reset", "mi_dv_encode_batch",
            "mi_dv_encode_frame", "mi_dv_encode_times", "mi_dv_encode_stats", "mi_dv_audio_batch", "mi_dv_audio_write_batch",
-           "mi_dv_audio_samples", "mi_dv_audio_times", "mi_dv_audio_copy_tables"]
+           "mi_dv_audio_samples", "mi_dv_audio_times", "mi_dv_audio_copy_tables", "mi_dv_meta_batch", "mi_dv_meta_write_batch",
+           "mi_dv_timecode_of", "mi_dv_meta_times"]
+META_INTS = 16  # include/mi_dv.h: MI_DV_META_INTS; the row: found mask, timecode h m s f, drop, y m d, h m s, wide, raw x 3
+META_HAS_TIMECODE, META_HAS_DATE, META_HAS_TIME, META_HAS_CONTROL = 1, 2, 4, 8
 AUDIO_PAIRS, AUDIO_PAIR_BYTES = 4, 8192  # include/mi_dv.h: MI_DV_AUDIO_PAIRS, MI_DV_AUDIO_PAIR_BYTES
 AUDIO_CHANNELS = {SYS_525_60: 1, SYS_625_50: 1, SYS_625_50_411: 1, SYS_525_60_422: 2, SYS_625_50_422: 2}  # DIF channels
 STA_ERRORS = 0x8080  # the default mask of held macroblocks: STA 0111 and 1111 (include/mi_dv.h: MI_DV_STA_ERRORS)
@@ -96,6 +99,10 @@ def load():
     L.mi_dv_audio_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     L.mi_dv_audio_copy_tables.argtypes = [vp, C.c_size_t]
     L.mi_dv_audio_copy_tables.restype = C.c_size_t
+    L.mi_dv_meta_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    L.mi_dv_meta_write_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_int]
+    L.mi_dv_timecode_of.argtypes = [C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_int)]
+    L.mi_dv_meta_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     _LIB = L
     return L
 
@@ -126,6 +133,16 @@ def audio_samples(system, samplerate, k):
     if n < 0:
         raise MiDvError(L.mi_dv_last_error(None).decode())
     return n
+
+
+def timecode_of(system, frame, drop=0):
+    """(hours, minutes, seconds, frames) of frame number `frame` (from 0) as write_meta_batch labels it: 25 or 30 frames a
+    second, drop 1 (525/60 systems only): SMPTE drop-frame; hours wrap at 24 (host-side)"""
+    L = load()
+    v = (C.c_int * 4)()
+    if L.mi_dv_timecode_of(system, frame, drop, v) != 0:
+        raise MiDvError(L.mi_dv_last_error(None).decode())
+    return tuple(v)
 
 
 def geometry(system):
@@ -423,6 +440,43 @@ class MiDv:
     def audio_times(self):
         """(total milliseconds, launches) of k_dv_audio_extract and k_dv_audio_write since the last call"""
         return self._times(self.L.mi_dv_audio_times)
+
+    # ---- timecode, recording date and time, aspect of resident frames (include/mi_dv.h; parity unpinned: the readers
+    # restate the reference's, the packs written are this repository's reading of IEC 61834) ----
+    def meta_batch(self, system, d_frames, n, d_meta):
+        """n resident frames -> d_meta[n][META_INTS] int32 (64-byte aligned): found mask, timecode h m s f, drop flag,
+        recording y m d, h m s, wide, the three packs' bytes 1..4; queued on the instance's stream"""
+        self._chk(self.L.mi_dv_meta_batch(self.c, system, d_frames, n, d_meta))
+
+    def write_meta_batch(self, system, d_frames, n, first_frame=0, drop=0, rec_seconds=-1, wide=0):
+        """the subcode and VAUX blocks of n resident frames, rewritten whole: frame k gets the timecode of frame number
+        first_frame + k and the recording time rec_seconds (from 1970-01-01, no time zone; negative: none) + k frames"""
+        self._chk(self.L.mi_dv_meta_write_batch(self.c, system, d_frames, n, first_frame, drop, rec_seconds, wide))
+
+    def extract_meta(self, frames, system):
+        """host frames -> an (n, META_INTS) int32 array as meta_batch writes it"""
+        fb = geometry(system)[0]
+        frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, fb)
+        n = frames.shape[0]
+        with self._resident(frames, n * META_INTS * 4) as (df, dm):
+            self.meta_batch(system, df, n, dm)
+            self.sync()
+            return self.d2h(dm, n * META_INTS * 4).view(np.int32).reshape(n, META_INTS)
+
+    def write_meta(self, frames, system, first_frame=0, drop=0, rec_seconds=-1, wide=0):
+        """host frames with timecode, recording date and time and aspect written into their subcode and VAUX blocks ->
+        host frames"""
+        fb = geometry(system)[0]
+        frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, fb)
+        n = frames.shape[0]
+        with self._resident(frames) as (df,):
+            self.write_meta_batch(system, df, n, first_frame, drop, rec_seconds, wide)
+            self.sync()
+            return self.d2h(df, n * fb).reshape(n, fb)
+
+    def meta_times(self):
+        """(total milliseconds, launches) of k_dv_meta_extract and k_dv_meta_write since the last call"""
+        return self._times(self.L.mi_dv_meta_times)
 
     def close(self):
         if self.c:

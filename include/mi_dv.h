@@ -76,8 +76,8 @@ int mi_dv_sync(mi_dv_ctx *c);
 int mi_dv_decode_batch(mi_dv_ctx *c, const void *d_frames, int n, void *d_pics);
 /* Device time of k_dv_decode: every mi_dv_decode_batch brackets its launch with HIP events on the instance's stream;
  * this sums them over the launches since the last call (synchronises, then forgets them).  Where nobody asks, the newest
- * 4096 launches are kept and older ones forgotten; so do mi_dv_hold_times, mi_dv_encode_times and mi_dv_audio_times, each
- * with 4096 of its own. */
+ * 4096 launches are kept and older ones forgotten; so do mi_dv_hold_times, mi_dv_encode_times, mi_dv_audio_times and
+ * mi_dv_meta_times, each with 4096 of its own. */
 int mi_dv_kernel_times(mi_dv_ctx *c, float *total_ms, int *launches);
 
 /* One frame from host memory into the caller's planes (Y, Cb, Cr) with the caller's strides — what a
@@ -184,7 +184,7 @@ int mi_dv_hold_reset(mi_dv_ctx *c);
  * the oracle.  Nothing here was compared with another DV implementation.  Every frame is complete: the video segments
  * (forward transforms, quantisation by the largest quantisation number at which a segment fits its 2,680 AC bits, the
  * three passes), block ids with the channel bit, DSF, the system's default APT and VAUX stype (mi_dv_kind_of answers the
- * system), zeros everywhere else: no subcode or VAUX content, and no audio until mi_dv_audio_write_batch.  flags: bit 0 lets a block take the 2-4-8 transform
+ * system), zeros everywhere else: no audio until mi_dv_audio_write_batch, no subcode or VAUX content until mi_dv_meta_write_batch.  flags: bit 0 lets a block take the 2-4-8 transform
  * where its two fields differ, bit 1 gives every block a class by its content (clear: class 0). */
 
 /* n pictures of the system's size, resident in device memory and back to back (the layout mi_dv_decode_batch_sys
@@ -238,6 +238,57 @@ int mi_dv_audio_times(mi_dv_ctx *c, float *total_ms, int *launches);
 /* The sound's layout table exactly as both kernels read it (csrc/dv_common.h, struct AudioTables: uint16 shuffle[2][12][9],
  * stride[2], min_samples[2][3]; row 0: 525/60, row 1: 625/50).  Host only, as mi_dv_copy_tables. */
 size_t mi_dv_audio_copy_tables(void *out, size_t cap);
+
+/* ---- timecode, recording date and time, aspect of resident frames, read and written on the device ----
+ *
+ * What include/mi_dvframe.h's mi_dv_timecode, mi_dv_date, mi_dv_time and mi_dv_pixel_aspect answer for one host frame,
+ * for a batch (the statement: tests/dvmeta.py); and the writer of the two subcode and three VAUX DIF blocks of every
+ * sequence, which the encoder leaves blank.  PARITY UNPINNED: the readers restate GetSSYBPack and its users
+ * (lib/dvframe.c:678-783, :460-471); the packs written are this repository's reading of IEC 61834-2/-4 from memory
+ * (nothing in the reference writes any), and what is checked is that this library's readers, on host and device, read
+ * them back. */
+enum {
+  MI_DV_META_INTS = 16,      /* int32 per frame in d_meta */
+  MI_DV_META_FOUND = 0,      /* MI_DV_META_HAS_* */
+  MI_DV_META_TC_HOUR = 1, MI_DV_META_TC_MINUTE = 2, MI_DV_META_TC_SECOND = 3, MI_DV_META_TC_FRAME = 4,
+  MI_DV_META_TC_DROP = 5,    /* bit 6 of the timecode pack's byte 1 */
+  MI_DV_META_YEAR = 6,       /* two digits with the reference's pivot: below 25 -> 20xx, else 19xx */
+  MI_DV_META_MONTH = 7, MI_DV_META_DAY = 8,
+  MI_DV_META_HOUR = 9, MI_DV_META_MINUTE = 10, MI_DV_META_SECOND = 11,
+  MI_DV_META_WIDE = 12,      /* 1: mi_dv_pixel_aspect would answer the 16:9 ratio */
+  MI_DV_META_TC_RAW = 13, MI_DV_META_DATE_RAW = 14, MI_DV_META_TIME_RAW = 15 /* bytes 1..4 of the pack, little-endian */
+};
+enum {
+  MI_DV_META_HAS_TIMECODE = 1, /* pack 0x13 in a subcode packet of channel 0 */
+  MI_DV_META_HAS_DATE = 2,     /* pack 0x62 */
+  MI_DV_META_HAS_TIME = 4,     /* pack 0x63 */
+  MI_DV_META_HAS_CONTROL = 8   /* the VAUX source control pack 0x61 at byte 80 * 5 + 48 + 5 */
+};
+/* n resident frames of `system` (4-byte aligned) -> d_meta[n][MI_DV_META_INTS] int32 (64-byte aligned, not overlapping the
+ * frames).  Each pack is the first in the host reader's order: sequence, subcode block, packet, over the sequences of
+ * channel 0.  Every field of a pack that was not found is 0.  Queued on the instance's stream; pair with mi_dv_sync.
+ * MI_DV_ERR_ARG, with nothing launched, for an unknown system, n out of 1..65535, NULL, misaligned or overlapping buffers. */
+int mi_dv_meta_batch(mi_dv_ctx *c, int system, const void *d_frames, int n, void *d_meta);
+/* Rewrites the two subcode and the three VAUX DIF blocks of every sequence of every channel of n resident frames, whole,
+ * and no other byte: ids as the encoder writes them; in the subcode packets timecode (0x13), recording date (0x62) and
+ * recording time (0x63) in turns; in the first and third VAUX block the packs 0x60 (DSF and the system's stype: the
+ * frame's kind stays what it was), 0x61 (the aspect: `wide`), 0x62, 0x63; FF elsewhere.  Frame k carries the timecode
+ * of frame number first_frame + k (25 or 30 frames a second; drop_frame 1, 525/60 systems only: SMPTE drop-frame) and
+ * the recording time rec_seconds + floor(k / frame rate), in seconds from 1970-01-01 00:00:00 with no time zone;
+ * rec_seconds below 0: no date and no time (the packs are FF x 5).  A year from 2025 on reads back as 19xx: the readers'
+ * pivot.  One call per run of consecutive frames.  Queued on the instance's stream: straight after mi_dv_encode_batch or
+ * mi_dv_audio_write_batch it needs no sync.  MI_DV_ERR_ARG, with nothing launched, for an unknown system, n out of
+ * 1..65535, a NULL or misaligned d_frames, drop_frame outside {0, 1} or 1 on a 625/50 system, first_frame below 0 or
+ * first_frame + n above 2^40, rec_seconds from 3155760000 (the year 2070) on, wide outside {0, 1}. */
+int mi_dv_meta_write_batch(mi_dv_ctx *c, int system, void *d_frames, int n, long long first_frame, int drop_frame,
+                           long long rec_seconds, int wide);
+/* The timecode of frame number `frame` (from 0) as the writer makes it: hours (wrapping at 24), minutes, seconds,
+ * frames.  Host only; MI_DV_ERR_ARG for an unknown system, a frame below 0, drop_frame outside {0, 1} or 1 on a 625/50
+ * system, a NULL hmsf. */
+int mi_dv_timecode_of(int system, long long frame, int drop_frame, int hmsf[4]);
+/* Device time of k_dv_meta_extract and k_dv_meta_write (one launch a batch call) since the last call, as
+ * mi_dv_kernel_times, which keeps counting k_dv_decode alone. */
+int mi_dv_meta_times(mi_dv_ctx *c, float *total_ms, int *launches);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,8 @@
  * pack extraction.  For one frame none of it is data-parallel, and this file runs on the host; it is
  * restated so that the DV rows of the scope table exist next to the RTjpeg path.  For a batch of
  * frames resident in device memory the audio de-shuffle also runs on the device: mi_dv_audio_batch
- * of mi_dv.h writes, byte for byte, what mi_dv_extract_audio here writes into zeroed buffers.  DV *pixel*
+ * of mi_dv.h writes, byte for byte, what mi_dv_extract_audio here writes into zeroed buffers, and mi_dv_meta_batch answers what
+ * mi_dv_timecode, mi_dv_date, mi_dv_time and mi_dv_pixel_aspect here answer.  DV *pixel*
  * decoding (row D4) is libavcodec's in the reference and is not part of this repository.
  *
  * PARITY UNPINNED: lib/dvframe.c cannot be compiled in the build container (it needs gavl
