@@ -31,6 +31,7 @@
 #include "rtj_runs_kernels.h"
 #include "rtj_spec_kernels.h"
 #include "rtj_tables.h"
+#include "rtj_walk_kernels.h"
 #include "rtj_host_buf.h"
 #include "rtj_host_switches.h"
 

@@ -1,10 +1,10 @@
-// rtj_decode_kernels.h — gfx950 kernels of the RTjpeg decode path.
+// rtj_decode_kernels.h — gfx950 kernels of the RTjpeg decode path: the transform.
 //
-//   k_index_walk   block-start index of every packet: RTjpeg_s2b's length rule
-//                  (lib/RTjpeg.c:157-186) driven by RTjpeg_decompressYUV420's block order
-//                  (lib/RTjpeg.c:2688-2749).
 //   k_decode       dequantise + 8x8 AAN inverse transform + plane scatter
 //                  (lib/RTjpeg.c:157-186, 2209-2332, 2688-2749), one lane per 8x8 block.
+//   transform_lo, transform_full   the transform of a live block, shared with k_decode_fmt (rtj_format_kernels.h).
+//
+// The block-start index the transform reads (k_index_walk and the walkers) is in rtj_walk_kernels.h.
 //
 // Integer only; no MFMA: the transform is a fixed 8-point butterfly network with rounding
 // after every product, not a contraction.
@@ -22,314 +22,6 @@ namespace mirtj {
 __constant__ uint8_t c_zz[64] = MIRTJ_ZZ_INIT;
 
 // ---------------------------------------------------------------------------------------
-// wave64 inclusive prefix sum with DPP row shifts + row broadcasts (no LDS)
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-  // within each row of 16 lanes: Hillis-Steele with row_shr 1,2,4,8 (out-of-row sources read 0)
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);
-  // lane 15 of rows 0 and 2 into every lane of rows 1 and 3
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);
-  // lane 31 into every lane of rows 2 and 3
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);
-  return x;
-}
-
-// number of coefficient slots a stream byte covers when it is read as a token (lib/RTjpeg.c:171-182):
-// 64..127 (int8 > 63) is a zero run of b-63, anything else is one coefficient
-__device__ __forceinline__ uint32_t token_weight(uint32_t b) {
-  return (b - 64u < 64u) ? b - 63u : 1u;
-}
-
-// ---------------------------------------------------------------------------------------
-// walk_blocks: one wave walks a stretch of the block chain of one packet.
-//
-// Lane i of the wave holds byte base+i of the stream (two 64-byte windows, "cur" and "nxt")
-// and the running sum W of token weights.  A block that starts at p with bt8 raw bytes ends at
-// the first byte e whose W reaches W[p+bt8] + (63-bt8): one compare + find-first-set per block.
-// The chain itself is serial (a block's length is only known once it has been read), so the
-// position lives in scalar registers and the vector unit is used 64 bytes at a time.
-// Walks blocks k0..k1-1 (k0 a multiple of 6) starting at byte p_start and writes out[k] = byte
-// offset of block k relative to the first data byte; with write_end also out[k1] = end position.
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void walk_blocks(const FrameDev& f, const uint8_t* __restrict__ stream,
-                                            const QTab* __restrict__ lut, uint32_t p_start, uint32_t k0,
-                                            uint32_t k1, bool write_end, uint32_t* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const uint8_t* g = stream + f.data_off;
-  const uint32_t len = f.data_len;
-  const uint32_t lb8 = (uint32_t)lut[f.qidx].lb8, cb8 = (uint32_t)lut[f.qidx].cb8;
-
-  auto fetch = [&](uint32_t pos) -> uint32_t {
-    const uint32_t i = pos + lane;
-    return i < len ? (uint32_t)g[i] : 0u;
-  };
-
-  uint32_t base = p_start;
-  uint32_t cur = fetch(base), nxt = fetch(base + 64u), pf1 = fetch(base + 128u), pf2 = fetch(base + 192u),
-           pf3 = fetch(base + 256u);
-  uint32_t Wc = wave_incl_scan(token_weight(cur));
-  uint32_t Wn = wave_incl_scan(token_weight(nxt)) + (uint32_t)__builtin_amdgcn_readlane((int)Wc, 63);
-
-  uint32_t p = p_start;  // current block start (uniform)
-  uint32_t ph = 0;       // block number within the macroblock, 0..5
-  uint32_t acc = 0;      // up to 64 offsets gathered one lane at a time, stored 256 B at once
-
-  for (uint32_t k = k0;; ++k) {
-    while (p - base >= 64u) {  // slide the two windows forward
-      base += 64u;
-      cur = nxt;
-      Wc = Wn;
-      nxt = pf1;
-      pf1 = pf2;
-      pf2 = pf3;
-      pf3 = fetch(base + 256u);
-      Wn = wave_incl_scan(token_weight(nxt)) + (uint32_t)__builtin_amdgcn_readlane((int)Wc, 63);
-    }
-    const bool last = k == k1;
-    if (!last || write_end) acc = (uint32_t)lane == (k & 63u) ? p : acc;
-    if ((k & 63u) == 63u || last) {
-      const uint32_t idx = (k & ~63u) + (uint32_t)lane;
-      const uint32_t top = last && !write_end ? k - 1u : k;  // k1 > k0 >= 0, so no wrap
-      if (idx >= k0 && idx <= top) out[idx] = acc;
-    }
-    if (last) break;
-
-    const uint32_t lp = p - base;
-    const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)lp);
-    const uint32_t bt8 = ph >= 4u ? cb8 : lb8;
-    ph = ph == 5u ? 0u : ph + 1u;
-    if (b0 == 0xFFu) {  // "unchanged" block: a single byte
-      p += 1u;
-      continue;
-    }
-    const uint32_t need = 63u - bt8;
-    if (need == 0u) {  // every coefficient is a raw byte
-      p += 64u;
-      continue;
-    }
-    const uint32_t iq = lp + bt8;  // last non-token byte of the block, 0..126
-    const uint32_t Wq = iq < 64u ? (uint32_t)__builtin_amdgcn_readlane((int)Wc, (int)iq)
-                                 : (uint32_t)__builtin_amdgcn_readlane((int)Wn, (int)(iq - 64u));
-    const uint32_t target = Wq + need;
-    const unsigned long long mc = __ballot(Wc >= target);
-    uint32_t e;
-    if (mc) {
-      e = (uint32_t)__builtin_ctzll(mc);
-    } else {
-      const unsigned long long mn = __ballot(Wn >= target);
-      e = 64u + (uint32_t)__builtin_ctzll(mn);  // W grows by >= 1 per byte, so mn != 0
-    }
-    p = base + e + 1u;
-  }
-}
-
-// The same walk, bounded by position instead of block count, for the speculative index's repairs
-// (rtj_spec_kernels.h): from byte p_start, taken to start a macroblock, every block start below `limit` sets its bit in
-// `bits` (LDS, zeroed by the caller; bit 31 - i of dword k = position 32 k + i relative to p_start, the first start
-// is position 0; starts at or past `span` relative positions are counted but not marked).  Returns the number of blocks.
-// take / tail: (index << 16 | offset) of the last unit-aligned start below `mid` / below `limit`, the unit being
-// the macroblock, or the block when lb8 == cb8.
-__device__ __forceinline__ uint32_t walk_record(const FrameDev& f, const uint8_t* __restrict__ stream,
-                                                const QTab* __restrict__ lut, uint32_t p_start, uint32_t mid,
-                                                uint32_t limit, uint32_t* bits, uint32_t span, uint32_t& take,
-                                                uint32_t& tail) {
-  const int lane = threadIdx.x & 63;
-  const uint8_t* g = stream + f.data_off;
-  const uint32_t len = f.data_len;
-  const uint32_t lb8 = (uint32_t)lut[f.qidx].lb8, cb8 = (uint32_t)lut[f.qidx].cb8;
-  auto fetch = [&](uint32_t pos) -> uint32_t {
-    const uint32_t i = pos + lane;
-    return i < len ? (uint32_t)g[i] : 0u;
-  };
-  uint32_t base = p_start;
-  uint32_t cur = fetch(base), nxt = fetch(base + 64u), pf1 = fetch(base + 128u), pf2 = fetch(base + 192u),
-           pf3 = fetch(base + 256u);
-  uint32_t Wc = wave_incl_scan(token_weight(cur));
-  uint32_t Wn = wave_incl_scan(token_weight(nxt)) + (uint32_t)__builtin_amdgcn_readlane((int)Wc, 63);
-  uint32_t p = p_start, ph = 0, k = 0;
-  const bool by_block = lb8 == cb8;
-  take = tail = 0;
-  while (p < limit) {
-    if (by_block || ph == 0u) {  // a unit-aligned record
-      const uint32_t v = (k << 16) | (p - p_start);
-      if (p < mid) take = v;
-      tail = v;
-    }
-    while (p - base >= 64u) {  // slide the two windows forward
-      base += 64u;
-      cur = nxt;
-      Wc = Wn;
-      nxt = pf1;
-      pf1 = pf2;
-      pf2 = pf3;
-      pf3 = fetch(base + 256u);
-      Wn = wave_incl_scan(token_weight(nxt)) + (uint32_t)__builtin_amdgcn_readlane((int)Wc, 63);
-    }
-    {
-      const uint32_t rel = p - p_start;  // wave-uniform: one lane marks it
-      if (lane == 0 && rel < span) bits[rel >> 5] |= 0x80000000u >> (rel & 31u);
-    }
-    k++;
-    const uint32_t lp = p - base;
-    const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)lp);
-    const uint32_t bt8 = ph >= 4u ? cb8 : lb8;
-    ph = ph == 5u ? 0u : ph + 1u;
-    if (b0 == 0xFFu) {  // "unchanged" block: a single byte
-      p += 1u;
-      continue;
-    }
-    const uint32_t need = 63u - bt8;
-    const uint32_t iq = lp + bt8;  // last non-token byte of the block, 0..126 (bt8 <= 15)
-    const uint32_t Wq = iq < 64u ? (uint32_t)__builtin_amdgcn_readlane((int)Wc, (int)iq)
-                                 : (uint32_t)__builtin_amdgcn_readlane((int)Wn, (int)(iq - 64u));
-    const uint32_t target = Wq + need;
-    const unsigned long long mc = __ballot(Wc >= target);
-    uint32_t e;
-    if (mc) {
-      e = (uint32_t)__builtin_ctzll(mc);
-    } else {
-      const unsigned long long mn = __ballot(Wn >= target);
-      e = 64u + (uint32_t)__builtin_ctzll(mn);  // W grows by >= 1 per byte, so mn != 0
-    }
-    p = base + e + 1u;
-  }
-  return k;
-}
-
-// walk_packet: walk_blocks for a whole packet, written for the issue rates of the scalar and the vector unit.  With
-// thousands of walkers resident the serial walk is bound by instruction issue (a SIMD issues one scalar and one vector
-// instruction per four cycles; walk_blocks' early-outs compile to ~46 scalar instructions per block, half of them
-// branches and flag shuffling).  Here:
-//   * a block is ONE straight path: the next position is selected between its two cases (unchanged block: 1 byte; else
-//     behind the byte whose weight sum reaches the target — tables whose blocks are all raw bytes are refused by the host,
-//     kMaxRawBytes) with scalar selects, and both windows are searched at once;
-//   * the macroblock's blocks are unrolled from FmtShape<Fmt> (kBlkPerMb - kChromaPlanes luma steps, then kChromaPlanes
-//     chroma steps: Y Y Y Y Cb Cr, Y Y Cb Cr, or Y alone), so the raw-byte count of a block is a loop constant;
-//   * of the window's bytes only "is 0xFF" is kept, as a lane mask in scalar registers (one compare per 64 bytes instead of
-//     a lane read per block), so nothing but the weight sums and the bytes in flight rotates when the window slides;
-//   * the stream is read through a buffer descriptor that returns 0 past the packet's end (no exec masking);
-//   * the offsets are gathered with v_writelane at a running lane and stored 64 at a time.
-// Bounds no stream reaches, for all three block patterns: the search of a block is entered with lp < 64, and a block is
-// at most 64 bytes (the host refuses tables with more than kMaxRawBytes raw coefficients, so a block always ends behind
-// a byte of the two windows), so the next lp is at most 127 and the slide loop runs at most once per block; the
-// macroblock loop runs f.nmb times.
-template <int Fmt>
-__device__ __forceinline__ void walk_packet(const FrameDev& f, const uint8_t* __restrict__ stream,
-                                            const QTab* __restrict__ lut, uint32_t* __restrict__ out) {
-  constexpr uint32_t kB = FmtShape<Fmt>::kBlkPerMb, kLuma = kB - FmtShape<Fmt>::kChromaPlanes;
-  static_assert((kLuma == 1u || kLuma == 2u || kLuma == 4u) && (kB == kLuma || kB == kLuma + 2u), "the step list below");
-  const uint32_t lane = threadIdx.x & 63u;
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(stream + f.data_off), 0, (int)f.data_len, 0x00020000);
-  // a stream byte as int8 (the range check of a raw buffer covers the vector offset only: the position goes there)
-  auto fetch = [&](uint32_t pos) -> int {
-    return (int)(int8_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(pos + lane), 0, 0);
-  };
-  // token_weight() of an int8: 64..127 is a zero run of b - 63, anything else (<= 63, negative) one coefficient
-  auto weight = [](int b) -> uint32_t {
-    const int x = b - 63;
-    return (uint32_t)(x < 1 ? 1 : x > 64 ? 64 : x);
-  };
-  const uint32_t lb8 = (uint32_t)lut[f.qidx].lb8, cb8 = (uint32_t)lut[f.qidx].cb8;
-  const uint32_t need_l = 63u - lb8, need_c = 63u - cb8;
-  uint32_t base = 0, Wc, Wn;
-  int pf1, pf2, pf3;
-  unsigned long long ffc, ffn;  // lanes of the two windows that hold 0xFF ("unchanged block" where a block starts)
-  {
-    const int cur = fetch(0u), nxt = fetch(64u);
-    pf1 = fetch(128u);
-    pf2 = fetch(192u);
-    pf3 = fetch(256u);
-    Wc = wave_incl_scan(weight(cur));
-    Wn = wave_incl_scan(weight(nxt)) + (uint32_t)__builtin_amdgcn_readlane((int)Wc, 63);
-    ffc = __ballot(cur == -1);
-    ffn = __ballot(nxt == -1);
-  }
-  uint32_t lp = 0;     // the current block's start, relative to base
-  uint32_t j = 0;      // offsets gathered in acc since the last store
-  uint32_t acc = 0;
-  uint32_t* o = out;   // where acc's lane 0 goes
-  auto flush = [&]() {
-    if (lane < j) o[lane] = acc;
-    o += j;
-    j = 0;
-  };
-  auto step = [&](const uint32_t bt8, const uint32_t need, const int c) {  // c: the block's number in its macroblock
-    while (lp >= 64u) {  // slide the two windows forward
-      base += 64u;
-      lp -= 64u;
-      const int b = pf1;
-      pf1 = pf2;
-      pf2 = pf3;
-      pf3 = fetch(base + 256u);
-      Wc = Wn;
-      ffc = ffn;
-      Wn = wave_incl_scan(weight(b)) + (uint32_t)__builtin_amdgcn_readlane((int)Wc, 63);
-      ffn = __ballot(b == -1);
-    }
-    asm("s_add_i32 m0, %2, %3\n\tv_writelane_b32 %0, %1, m0" : "+v"(acc) : "s"(base + lp), "s"(j), "n"(c) : "m0", "scc");
-    const uint32_t iq = lp + bt8;  // last non-token byte of the block, 0..78
-    const uint32_t wq_c = (uint32_t)__builtin_amdgcn_readlane((int)Wc, (int)(iq & 63u));
-    const uint32_t wq_n = (uint32_t)__builtin_amdgcn_readlane((int)Wn, (int)(iq & 63u));
-    const uint32_t target = (iq < 64u ? wq_c : wq_n) + need;
-    // first byte whose sum reaches the target: in the first window, else in the second (W grows by >= 1 per byte, so
-    // it is there); find-first-set of nothing is 0xFFFFFFFF
-    const unsigned long long mc = __ballot(Wc >= target), mn = __ballot(Wn >= target);
-    uint32_t ec, en;
-    asm("s_ff1_i32_b64 %0, %1" : "=s"(ec) : "s"(mc));
-    asm("s_ff1_i32_b64 %0, %1" : "=s"(en) : "s"(mn));
-    en |= 64u;
-    const uint32_t e = ec < en ? ec : en;
-    asm("s_bitcmp1_b64 %1, %2\n\ts_cselect_b32 %0, %3, %4" : "=s"(lp) : "s"(ffc), "s"(lp), "s"(lp + 1u), "s"(e + 1u) : "scc");
-  };
-  for (uint32_t mb = 0; mb < f.nmb; ++mb) {
-    if (j > 64u - kB) flush();
-    // kLuma (4, 2 or 1) luma steps, then the chroma pair.  Written out: as a loop over the block number, unrolled by
-    // the compiler, every step of the 4:2:0 walker compiles to one more scalar instruction.
-    step(lb8, need_l, 0);
-    if constexpr (kLuma > 1u) step(lb8, need_l, 1);
-    if constexpr (kLuma > 2u) {
-      step(lb8, need_l, 2);
-      step(lb8, need_l, 3);
-    }
-    if constexpr (kB > kLuma) {
-      step(cb8, need_c, (int)kLuma);
-      step(cb8, need_c, (int)kLuma + 1);
-    }
-    j += kB;
-  }
-  if (j > 63u) flush();
-  asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(acc) : "s"(base + lp), "s"(j) : "m0");  // the end
-  j += 1u;
-  flush();
-}
-
-// Whole packet by one wave: the simple (serial) index, kept as the A/B baseline of the parallel one.
-__global__ __launch_bounds__(64) void k_index_walk(const FrameDev* __restrict__ frames,
-                                                    const uint8_t* __restrict__ stream,
-                                                    const QTab* __restrict__ lut,
-                                                    uint32_t* __restrict__ blkoff) {
-  const FrameDev f = frames[blockIdx.x];
-  walk_packet<kFmtYUV420>(f, stream, lut, blkoff + f.blk_base);
-}
-
-// The packets of a to-do list, a wave each (grid-stride): what k_spec_policy hands the serial walker when the list is long.
-__global__ __launch_bounds__(64) void k_index_walk_todo(const FrameDev* __restrict__ frames,
-                                                         const uint8_t* __restrict__ stream,
-                                                         const QTab* __restrict__ lut, uint32_t* __restrict__ blkoff,
-                                                         const uint32_t* __restrict__ todo,
-                                                         const uint32_t* __restrict__ ntodo) {
-  const uint32_t n = *ntodo;
-  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-    const FrameDev f = frames[todo[i]];
-    walk_packet<kFmtYUV420>(f, stream, lut, blkoff + f.blk_base);
-  }
-}
-
-// ---------------------------------------------------------------------------------------
 // 8-point inverse AAN butterfly (lib/RTjpeg.c:2240-2283 for columns, :2290-2327 for rows;
 // constants :1196-1199, MULTIPLY :1206).  Every multiplicand stays below 2^23 in magnitude
 // for any int16 input block (tests/test_bounds.py), so the 24-bit multiplier is exact and
@@ -339,11 +31,7 @@ __global__ __launch_bounds__(64) void k_index_walk_todo(const FrameDev* __restri
 // otherwise fall back to the quarter-rate 32-bit multiplier for the whole row pass.
 __device__ __forceinline__ int mulr8(int x, int c) {
   int r;
-#ifdef MIRTJ_NOP_AFTER_MAD
-  asm("v_mad_i32_i24 %0, %1, %2, %3\n\ts_nop 0" : "=v"(r) : "v"(x), "s"(c), "v"(128));
-#else
   asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(c), "v"(128));
-#endif
   return r >> 8;
 }
 
@@ -353,6 +41,8 @@ __device__ __forceinline__ int mul24(int a, int b) {  // both operands inside th
   return r;
 }
 
+// The readable statement of the butterfly.  No kernel calls it (the passes of rtj_idct_asm.h and rtj_idct_pk.h compute
+// the same in their own instruction order); tools/ubench/idct_rate.hip and idct_asm_rate.hip keep it as the comparator.
 __device__ __forceinline__ void idct8(int x0, int x1, int x2, int x3, int x4, int x5, int x6, int x7,
                                       int (&y)[8]) {
   const int s04 = x0 + x4, d04 = x0 - x4;
@@ -389,22 +79,6 @@ __device__ __forceinline__ void idct8_lo(int x0, int x1, int x2, int x3, int (&y
   y[4] = e3 + o4; y[3] = e3 - o4;
 }
 
-// The same again when x3 is zero as well (mulr8(0, 669) == 0), for waves whose blocks stay inside the low 3x3:
-// chroma at high quality.
-__device__ __forceinline__ void idct8_lo3(int x0, int x1, int x2, int (&y)[8]) {
-  const int r26 = mulr8(x2, 362) - x2;
-  const int e0 = x0 + x2, e3 = x0 - x2, e1 = x0 + r26, e2 = x0 - r26;
-  const int m = mulr8(x1, 362);
-  const int z5 = mulr8(x1, 473);
-  const int o6 = z5 - x1;
-  const int o5 = m - o6;
-  const int o4 = mulr8(x1, 277) - z5 + o5;
-  y[0] = e0 + x1; y[7] = e0 - x1;
-  y[1] = e1 + o6; y[6] = e1 - o6;
-  y[2] = e2 + o5; y[5] = e2 - o5;
-  y[4] = e3 + o4; y[3] = e3 - o4;
-}
-
 // DESCALE + int16 narrowing + clamp 16..235 (lib/RTjpeg.c:1201-1205).  The +4 rounding term
 // was folded into the DC coefficient before the column pass, so only the shift remains:
 // bits [18:3] sign-extended == (int16_t)(v >> 3).
@@ -417,12 +91,6 @@ __device__ __forceinline__ uint32_t px(int v) {
 
 __device__ __forceinline__ uint32_t lshl_or(uint32_t a, int sh, uint32_t b) {  // (a << sh) | b
   uint32_t r;
-#ifdef MIRTJ_NOP_AFTER_PACK
-  if (sh == 16) {
-    asm("v_lshl_or_b32 %0, %1, %2, %3\n\ts_nop 0" : "=v"(r) : "v"(a), "n"(sh), "v"(b));
-    return r;
-  }
-#endif
   asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "n"(sh), "v"(b));
   return r;
 }
@@ -638,18 +306,18 @@ template <class Put>
 __device__ __forceinline__ void transform_lo(const uint4* my, const IdctK& K, const IdctPK& KP, Put&& putp) {
   auto putr = [&](const int (&y)[8]) {
     uint2 o;
+    // three shift-or instructions per four pixels, spelled out: the compiler's own choice for
+    // a | b<<8 | c<<16 | d<<24 is two shifts, an or3 and a shift-or
     o.x = lshl_or(lshl_or(px(y[3]), 8, px(y[2])), 16, lshl_or(px(y[1]), 8, px(y[0])));
     o.y = lshl_or(lshl_or(px(y[7]), 8, px(y[6])), 16, lshl_or(px(y[5]), 8, px(y[4])));
     putp(o);
   };
-  (void)putr;
   // rows 0-3 of the column pairs (0, 1) and (2, 3)
   const uint4 qa = my[0], qb = my[2];
   // anything in row 3 or column 3?
   const uint32_t t3 = qa.w | qb.w | ((qb.x | qb.y | qb.z) & 0xFFFF0000u);
   if (!__any(t3 != 0u)) {
     // ---- three-input transform: columns 0-2 in, rows of three in ----
-#if MIRTJ_PK_IDCT
     const bool fits = __all(pk_range_lo3(qa, qb, KP));
     if (fits) {
       // two columns, then two rows, to a register (rtj_idct_pk.h)
@@ -663,11 +331,8 @@ __device__ __forceinline__ void transform_lo(const uint4* my, const IdctK& K, co
         putp(o0);
         putp(o1);
       }
-    } else
-#endif
-    {
+    } else {
       int ws[8][3];
-#if MIRTJ_ASM_IDCT
       {
         int y[8];
         idct8_lo3_col<true, false>(qa.x, qa.y, qa.z, y, K);
@@ -682,25 +347,6 @@ __device__ __forceinline__ void transform_lo(const uint4* my, const IdctK& K, co
       }
 #pragma unroll
       for (int r = 0; r < 8; r++) putp(idct8_lo3_row_px(ws[r][0], ws[r][1], ws[r][2], K));
-#else
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        const uint4& q = c < 2 ? qa : qb;
-        int x0 = half16(q.x, c & 1);
-        const int x1 = half16(q.y, c & 1), x2 = half16(q.z, c & 1);
-        if (c == 0) x0 += 4;  // DESCALE's rounding term, carried through both linear DC paths
-        int y[8];
-        idct8_lo3(x0, x1, x2, y);
-#pragma unroll
-        for (int r = 0; r < 8; r++) ws[r][c] = y[r];
-      }
-#pragma unroll
-      for (int r = 0; r < 8; r++) {
-        int y[8];
-        idct8_lo3(ws[r][0], ws[r][1], ws[r][2], y);
-        putr(y);
-      }
-#endif
     }
   } else {
     // ---- four-input transform: columns 0-3 in, rows of four in ----
@@ -723,6 +369,77 @@ __device__ __forceinline__ void transform_lo(const uint4* my, const IdctK& K, co
       putr(y);
     }
   }
+}
+
+// The full 8x8 transform of a live block: `my` is the lane's coefficient scratch (lane `lane` of `s_lds`), the eight rows
+// are handed to `put` (clamped and packed, row 0 first).  Called by the lanes that have a live block.  Where every such
+// block of the wave is inside the packed passes' 16-bit budget (pk_range_full, rtj_idct_pk.h: every legal picture) the
+// packed passes run and the result is true.  Otherwise the result is false, and
+//   kOwnPasses: the one-value-per-register passes (rtj_idct_asm.h) ran instead;
+//   else:       nothing was stored — the caller leaves the part to k_decode_list (DecList above).  Those passes size the
+//               register file of every path of a kernel that holds them.
+template <bool kOwnPasses, class Put>
+__device__ __forceinline__ bool transform_full(const uint4* my, uint32_t* s_lds, int lane, const IdctK& K,
+                                               const IdctPK& KP, Put&& put) {
+  uint4 q[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) q[i] = my[i];
+  const bool packed = __all(pk_range_full(q, KP));  // wave-uniform
+  if (packed) {
+    // ---- column pass on the four column pairs, as they lie in the scratch (rtj_idct_pk.h) ----
+    uint32_t yy[4][8];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      uint32_t x[8] = {q[2 * j].x,     q[2 * j].y,     q[2 * j].z,     q[2 * j].w,
+                       q[2 * j + 1].x, q[2 * j + 1].y, q[2 * j + 1].z, q[2 * j + 1].w};
+      if (j == 0) idct8_pk_col<true>(x, KP);
+      else idct8_pk_col<false>(x, KP);
+#pragma unroll
+      for (int r = 0; r < 8; r++) yy[j][r] = x[r];
+    }
+    // ---- row pass on the four row pairs + scatter ----
+#pragma unroll
+    for (int r = 0; r < 8; r += 2) {
+      uint2 o0, o1;
+      uint32_t ya[4] = {yy[0][r], yy[1][r], yy[2][r], yy[3][r]};
+      uint32_t yb[4] = {yy[0][r + 1], yy[1][r + 1], yy[2][r + 1], yy[3][r + 1]};
+      idct8_pk_row_px(ya, yb, o0, o1, KP);
+      put(o0);
+      put(o1);
+    }
+  }
+  if (kOwnPasses && !packed) {
+    // ---- column pass: column c is one half of the 16-byte pieces c & ~1 (rows 0-3) and (c & ~1) + 1 (rows 4-7) ----
+    // Two rounds, rows 0-3 and rows 4-7, each with a column pass of its own: this path is the rare one (a block
+    // outside the 16-bit budget), and 32 + 32 registers of column results are what the kernel's register count —
+    // and with it the waves per SIMD of EVERY path — would be sized for.  (The scratch is read again, through
+    // an address the compiler cannot tell from the one above, or the 32 registers of the range test stay alive
+    // as well.)
+    uint32_t again = (uint32_t)lane * (uint32_t)(kCoefStride * 2);
+    asm volatile("" : "+v"(again));
+    const uint4* mq = (const uint4*)((const uint8_t*)s_lds + again);
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+      int ws[4][8];
+      int y[8];
+      idct8_col<true, false>(mq[0], mq[1], y, K);
+#pragma unroll
+      for (int r = 0; r < 4; r++) ws[r][0] = y[4 * half + r];
+#pragma unroll
+      for (int c = 1; c < 8; c++) {
+        if (c & 1) idct8_col<false, true>(mq[c - 1], mq[c], y, K);
+        else idct8_col<false, false>(mq[c], mq[c + 1], y, K);
+#pragma unroll
+        for (int r = 0; r < 4; r++) ws[r][c] = y[4 * half + r];
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+        put(idct8_row_px(ws[r][0], ws[r][1], ws[r][2], ws[r][3], ws[r][4], ws[r][5], ws[r][6], ws[r][7], K));
+      asm volatile("" : "+v"(again));  // (keeps the second round's column pass from being merged into the first)
+      mq = (const uint4*)((const uint8_t*)s_lds + again);
+    }
+  }
+  return packed;
 }
 
 // vector-memory stores every transform variant of decode_wave issues per live wave and iteration (eight rows of 8 bytes
@@ -1125,103 +842,12 @@ __device__ __forceinline__ void decode_wave(uint32_t* __restrict__ s_lds, const 
       };
       const IdctK K{362, 473, -669, 277, 128, 235};
       const IdctPK KP = idct_pk_constants();
-      auto put_row = [&](const int (&y)[8]) {
-        uint2 o;
-        // three shift-or instructions per four pixels, spelled out: the compiler's own choice for
-        // a | b<<8 | c<<16 | d<<24 is two shifts, an or3 and a shift-or
-        o.x = lshl_or(lshl_or(px(y[3]), 8, px(y[2])), 16, lshl_or(px(y[1]), 8, px(y[0])));
-        o.y = lshl_or(lshl_or(px(y[7]), 8, px(y[6])), 16, lshl_or(px(y[5]), 8, px(y[4])));
-        put_packed(o);
-      };
 
       if (lo) {
         transform_lo(my, K, KP, put_packed);
       } else {
-        bool packed = false;
-#if MIRTJ_PK_IDCT
-        uint4 q[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) q[i] = my[i];
-        packed = __all(pk_range_full(q, KP));  // wave-uniform
-        if (packed) {
-          // ---- column pass on the four column pairs, as they lie in the scratch (rtj_idct_pk.h) ----
-          uint32_t yy[4][8];
-#pragma unroll
-          for (int j = 0; j < 4; j++) {
-            uint32_t x[8] = {q[2 * j].x,     q[2 * j].y,     q[2 * j].z,     q[2 * j].w,
-                             q[2 * j + 1].x, q[2 * j + 1].y, q[2 * j + 1].z, q[2 * j + 1].w};
-            if (j == 0) idct8_pk_col<true>(x, KP);
-            else idct8_pk_col<false>(x, KP);
-#pragma unroll
-            for (int r = 0; r < 8; r++) yy[j][r] = x[r];
-          }
-          // ---- row pass on the four row pairs + scatter ----
-#pragma unroll
-          for (int r = 0; r < 8; r += 2) {
-            uint2 o0, o1;
-            uint32_t ya[4] = {yy[0][r], yy[1][r], yy[2][r], yy[3][r]};
-            uint32_t yb[4] = {yy[0][r + 1], yy[1][r + 1], yy[2][r + 1], yy[3][r + 1]};
-            idct8_pk_row_px(ya, yb, o0, o1, KP);
-            put_packed(o0);
-            put_packed(o1);
-          }
-        }
-#endif
+        const bool packed = transform_full<!kList>(my, s_lds, lane, K, KP, put_packed);
         if (kList && !packed) rows_stored = false;  // not this kernel's business: the whole part goes to k_decode_list
-        if (!kList && !packed) {
-          // ---- column pass: column c is one half of the 16-byte pieces c & ~1 (rows 0-3) and (c & ~1) + 1 (rows 4-7) ----
-          // Two rounds, rows 0-3 and rows 4-7, each with a column pass of its own: this path is the rare one (a block
-          // outside the 16-bit budget), and 32 + 32 registers of column results are what the kernel's register count —
-          // and with it the waves per SIMD of EVERY path — would be sized for.  (The scratch is read again, through
-          // an address the compiler cannot tell from the one above, or the 32 registers of the range test stay alive
-          // as well.)
-          uint32_t again = (uint32_t)lane * (uint32_t)(kCoefStride * 2);
-          asm volatile("" : "+v"(again));
-          const uint4* my = (const uint4*)((const uint8_t*)s_lds + again);
-#if MIRTJ_ASM_IDCT
-#pragma unroll
-          for (int half = 0; half < 2; half++) {
-            int ws[4][8];
-            int y[8];
-            idct8_col<true, false>(my[0], my[1], y, K);
-#pragma unroll
-            for (int r = 0; r < 4; r++) ws[r][0] = y[4 * half + r];
-#pragma unroll
-            for (int c = 1; c < 8; c++) {
-              if (c & 1) idct8_col<false, true>(my[c - 1], my[c], y, K);
-              else idct8_col<false, false>(my[c], my[c + 1], y, K);
-#pragma unroll
-              for (int r = 0; r < 4; r++) ws[r][c] = y[4 * half + r];
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-              put_packed(idct8_row_px(ws[r][0], ws[r][1], ws[r][2], ws[r][3], ws[r][4], ws[r][5], ws[r][6], ws[r][7], K));
-            asm volatile("" : "+v"(again));  // (keeps the second round's column pass from being merged into the first)
-            my = (const uint4*)((const uint8_t*)s_lds + again);
-          }
-#else
-          int ws[8][8];
-#pragma unroll
-          for (int c = 0; c < 8; c++) {
-            const uint4 a = my[c & ~1], b = my[(c & ~1) + 1];
-            int x0 = half16(a.x, c & 1);
-            const int x1 = half16(a.y, c & 1), x2 = half16(a.z, c & 1), x3 = half16(a.w, c & 1);
-            const int x4 = half16(b.x, c & 1), x5 = half16(b.y, c & 1), x6 = half16(b.z, c & 1), x7 = half16(b.w, c & 1);
-            if (c == 0) x0 += 4;  // DESCALE's rounding term, carried through both linear DC paths
-            int y[8];
-            idct8(x0, x1, x2, x3, x4, x5, x6, x7, y);
-#pragma unroll
-            for (int r = 0; r < 8; r++) ws[r][c] = y[r];
-          }
-          // ---- row pass + scatter ----
-#pragma unroll
-          for (int r = 0; r < 8; r++) {
-            int y[8];
-            idct8(ws[r][0], ws[r][1], ws[r][2], ws[r][3], ws[r][4], ws[r][5], ws[r][6], ws[r][7], y);
-            put_row(y);
-          }
-#endif
-        }
       }
     }
     // (appended behind the counted wait, or on the way out: the append is an atomic and a store, and nothing but the row

@@ -3,7 +3,7 @@
 //   RTjpeg_decompressYUV422 (lib/RTjpeg.c:2639-2686)  macroblock = 16x8 pixels: Y, Y, Cb, Cr; chroma planes w/2 x h
 //   RTjpeg_decompress8      (lib/RTjpeg.c:2751-2772)  8x8 luma blocks in raster order, one plane
 //
-//   k_index_fmt<Fmt>    block-start index: walk_packet<Fmt> (rtj_decode_kernels.h), one wave per packet, packets side by
+//   k_index_fmt<Fmt>    block-start index: walk_packet<Fmt> (rtj_walk_kernels.h), one wave per packet, packets side by
 //                       side (grid-stride).
 //   k_decode_fmt<Fmt>   dequantise + inverse transform + plane scatter, one lane per 8x8 block, one wave per part of a
 //                       group.  The arithmetic is the 4:2:0 path's: the packed passes of rtj_idct_pk.h behind their
@@ -19,6 +19,7 @@
 
 #include "rtj_common.h"
 #include "rtj_decode_kernels.h"
+#include "rtj_walk_kernels.h"
 
 namespace mirtj {
 
@@ -170,60 +171,7 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_fmt(const FrameDev* __re
     if (lo) {
       transform_lo(my, K, KP, put_packed);
     } else {
-      uint4 q[8];
-#pragma unroll
-      for (int i = 0; i < 8; i++) q[i] = my[i];
-      const bool packed = __all(pk_range_full(q, KP));  // wave-uniform: every live block inside the 16-bit budget
-      if (packed) {
-        // ---- column pass on the four column pairs, as they lie in the scratch (rtj_idct_pk.h) ----
-        uint32_t yy[4][8];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          uint32_t x[8] = {q[2 * j].x,     q[2 * j].y,     q[2 * j].z,     q[2 * j].w,
-                           q[2 * j + 1].x, q[2 * j + 1].y, q[2 * j + 1].z, q[2 * j + 1].w};
-          if (j == 0) idct8_pk_col<true>(x, KP);
-          else idct8_pk_col<false>(x, KP);
-#pragma unroll
-          for (int r = 0; r < 8; r++) yy[j][r] = x[r];
-        }
-        // ---- row pass on the four row pairs + scatter ----
-#pragma unroll
-        for (int r = 0; r < 8; r += 2) {
-          uint2 o0, o1;
-          uint32_t ya[4] = {yy[0][r], yy[1][r], yy[2][r], yy[3][r]};
-          uint32_t yb[4] = {yy[0][r + 1], yy[1][r + 1], yy[2][r + 1], yy[3][r + 1]};
-          idct8_pk_row_px(ya, yb, o0, o1, KP);
-          put_packed(o0);
-          put_packed(o1);
-        }
-      } else {
-        // ---- the one-value-per-register passes, in two rounds (rows 0-3, rows 4-7) as in decode_wave: the scratch is
-        // read again through an address the compiler cannot tell from the one above, so that the range test's 32
-        // registers do not stay alive next to the column results ----
-        uint32_t again = lane * (uint32_t)(kCoefStride * 2);
-        asm volatile("" : "+v"(again));
-        const uint4* mq = (const uint4*)((const uint8_t*)s_lds + again);
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-          int ws[4][8];
-          int y[8];
-          idct8_col<true, false>(mq[0], mq[1], y, K);
-#pragma unroll
-          for (int r = 0; r < 4; r++) ws[r][0] = y[4 * half + r];
-#pragma unroll
-          for (int c = 1; c < 8; c++) {
-            if (c & 1) idct8_col<false, true>(mq[c - 1], mq[c], y, K);
-            else idct8_col<false, false>(mq[c], mq[c + 1], y, K);
-#pragma unroll
-            for (int r = 0; r < 4; r++) ws[r][c] = y[4 * half + r];
-          }
-#pragma unroll
-          for (int r = 0; r < 4; r++)
-            put_packed(idct8_row_px(ws[r][0], ws[r][1], ws[r][2], ws[r][3], ws[r][4], ws[r][5], ws[r][6], ws[r][7], K));
-          asm volatile("" : "+v"(again));
-          mq = (const uint4*)((const uint8_t*)s_lds + again);
-        }
-      }
+      transform_full<true>(my, s_lds, (int)lane, K, KP, put_packed);
     }
   }
 }

@@ -1,6 +1,7 @@
 // rtj_idct_asm.h — the 8-point inverse AAN butterfly of RTjpeg_idct (lib/RTjpeg.c:2209-2332) as hand-ordered gfx950
-// instruction blocks.  Same arithmetic as idct8 / idct8_lo / idct8_lo3 / px in rtj_decode_kernels.h (which stay as the
-// readable statement of it and as the A/B baseline, -DMIRTJ_ASM_IDCT=0); what differs is the ORDER of instructions.
+// instruction blocks.  Same arithmetic as idct8 / idct8_lo / px in rtj_decode_kernels.h (idct8 stays as the readable
+// statement of it, idct8_lo and px run the four-input transform; the build that ran the whole transform on them was the
+// A/B baseline of these blocks and is gone); what differs is the ORDER of instructions.
 //
 // Why the order matters (tools/ubench/valu_snop.hip, valu_mix*.hip; profiles/r02/ubench_*):
 //   * plain 32-bit add / sub / shift / logic, and 16-bit add / min / max, issue at ~1.0 ns per wave64 instruction per
@@ -20,23 +21,14 @@
 
 namespace mirtj {
 
-#ifndef MIRTJ_ASM_IDCT
-#define MIRTJ_ASM_IDCT 1
-#endif
-
 // wave-uniform constants the blocks take as operands: FIX_1_414213562 = 362, FIX_1_847759065 = 473,
 // -FIX_2_613125930 = -669, FIX_1_082392200 = 277 (lib/RTjpeg.c:1196-1199) in scalar registers; 128 (MULTIPLY's
 // rounding term, :1206) and 235 (RL's upper bound, :1205) in vector registers (a VOP3 takes one scalar operand).
 // Where the transform's multipliers and byte selectors live.  They are wave-uniform and the compiler keeps them in scalar
-// registers ("s").  k_decode is short of those (round 2's kernel paid for 50 spilled scalars in v_writelane / v_readlane;
-// the batch instantiation is down to 10 since the launch shape became a template parameter), and it has vector
-// registers to spare below the 128 that four waves per SIMD allow, so -DMIRTJ_K_IN_VGPR makes them vector operands:
-// measured, that leaves 7 spills instead of 10 and is 0.5 % SLOWER (profiles/r03/ab_spills.txt) — the default stays "s".
-#ifdef MIRTJ_K_IN_VGPR
-#define MIRTJ_KREG(x) "v"(x)
-#else
-#define MIRTJ_KREG(x) "s"(x)
-#endif
+// registers: the blocks take them as "s" operands.  k_decode is short of those (round 2's kernel paid for 50 spilled
+// scalars in v_writelane / v_readlane; the batch instantiation is down to 10 since the launch shape became a template
+// parameter), and it has vector registers to spare below the 128 that four waves per SIMD allow; as vector operands
+// they left 7 spills instead of 10 and measured 0.5 % SLOWER (profiles/r03/ab_spills.txt).
 struct IdctK {
   int k362, k473, km669, k277;  // scalar
   int c128, c235;               // vector
@@ -104,18 +96,11 @@ struct IdctK {
   "v_sub_u32 " t0 ", " t0 ", " x1 "\n\t" /* y3 = e3 - o4 */
 
 // DESCALE + int16 narrowing + clamp 16..235 of eight values (the +4 was folded into the DC coefficient), packed
-// into two dwords.  Two forms:
-//   MIRTJ_PX_FORM 0: v_bfe_i32 (bits 18:3, sign-extended = int16(v >> 3)), v_med3_i32, and three
-//     v_lshl_or_b32 per four pixels: 22 instructions per row, the fewest — and while other waves of the SIMD keep
-//     expensive instructions in flight every instruction costs the same (rtj_decode_kernels.h, "what an instruction
-//     costs"), so the count is what matters;
-//   MIRTJ_PX_FORM 1 (default; the two measure alike in k_decode, 4.54-4.56 against 4.56-4.60 ms): v_ashrrev_i32 3, v_max_i16 16 (both plain: v >> 3 leaves int16(v >> 3) in the low half, which
-//     the 16-bit max / min read as signed) and a v_min_i16 whose SDWA destination select writes the byte straight
-//     into the packed dword: 24 instructions, 16 of them plain — the faster form when the SIMD's waves run in step.
-#ifndef MIRTJ_PX_FORM
-#define MIRTJ_PX_FORM 1
-#endif
-#if MIRTJ_PX_FORM == 1
+// into two dwords: v_ashrrev_i32 3, v_max_i16 16 (both plain: v >> 3 leaves int16(v >> 3) in the low half, which
+// the 16-bit max / min read as signed) and a v_min_i16 whose SDWA destination select writes the byte straight
+// into the packed dword: 24 instructions per row, 16 of them plain.  (The other form tried — v_bfe_i32, v_med3_i32
+// and three v_lshl_or_b32 per four pixels, 22 instructions — measured alike in k_decode: 4.56-4.60 against
+// 4.54-4.56 ms.)
 #define MIRTJ_PX1(Y) "v_ashrrev_i32 " Y ", 3, " Y "\n\tv_max_i16 " Y ", 16, " Y "\n\t"
 #define MIRTJ_PACK1(O, Y, SEL, KEEP) \
   "v_min_i16_sdwa " O ", " Y ", %[c235] dst_sel:" SEL " dst_unused:" KEEP " src0_sel:WORD_0 src1_sel:WORD_0\n\t"
@@ -126,21 +111,9 @@ struct IdctK {
   MIRTJ_PACK1("%[o0]", y2, "BYTE_2", "UNUSED_PRESERVE") MIRTJ_PACK1("%[o1]", y6, "BYTE_2", "UNUSED_PRESERVE")   \
   MIRTJ_PACK1("%[o0]", y3, "BYTE_3", "UNUSED_PRESERVE") MIRTJ_PACK1("%[o1]", y7, "BYTE_3", "UNUSED_PRESERVE")   \
   MIRTJ_WAIT_PX
-#else
-#define MIRTJ_PX1(Y) "v_bfe_i32 " Y ", " Y ", 3, 16\n\tv_med3_i32 " Y ", " Y ", 16, %[c235]\n\t"
-#define MIRTJ_PX_PACK(y0, y1, y2, y3, y4, y5, y6, y7)                                                            \
-  MIRTJ_PX1(y0) MIRTJ_PX1(y1) MIRTJ_PX1(y2) MIRTJ_PX1(y3) MIRTJ_PX1(y4) MIRTJ_PX1(y5) MIRTJ_PX1(y6) MIRTJ_PX1(y7) \
-  "v_lshl_or_b32 " y1 ", " y1 ", 8, " y0 "\n\t"                                                                  \
-  "v_lshl_or_b32 " y3 ", " y3 ", 8, " y2 "\n\t"                                                                  \
-  "v_lshl_or_b32 " y5 ", " y5 ", 8, " y4 "\n\t"                                                                  \
-  "v_lshl_or_b32 " y7 ", " y7 ", 8, " y6 "\n\t"                                                                  \
-  "v_lshl_or_b32 %[o0], " y3 ", 16, " y1 "\n\t"                                                                  \
-  "v_lshl_or_b32 %[o1], " y7 ", 16, " y5 "\n\t"                                                                  \
-  MIRTJ_WAIT_PX
-#endif
 
 #define MIRTJ_K_OPERANDS \
-  [k362] MIRTJ_KREG(K.k362), [k473] MIRTJ_KREG(K.k473), [km669] MIRTJ_KREG(K.km669), [k277] MIRTJ_KREG(K.k277), [c128] "v"(K.c128), [c235] "v"(K.c235)
+  [k362] "s"(K.k362), [k473] "s"(K.k473), [km669] "s"(K.km669), [k277] "s"(K.k277), [c128] "v"(K.c128), [c235] "v"(K.c235)
 
 // ---- row pass on eight int32 values + descale, clamp, pack: one row of the block as two dwords ----
 __device__ __forceinline__ uint2 idct8_row_px(int x0, int x1, int x2, int x3, int x4, int x5, int x6, int x7,
@@ -215,7 +188,7 @@ __device__ __forceinline__ void idct8_col(const uint4& a, const uint4& b, int (&
   y[0] = x2; y[1] = x3; y[2] = x5; y[3] = t0; y[4] = x7; y[5] = x0; y[6] = x4; y[7] = x6;
 }
 
-// ---- the same when only x0, x1, x2 can be non-zero (idct8_lo3: every term the others feed vanishes exactly) ----
+// ---- the same when only x0, x1, x2 can be non-zero (every term the others feed vanishes exactly) ----
 #ifndef MIRTJ_NOP_LO3
 #define MIRTJ_NOP_LO3 6
 #endif

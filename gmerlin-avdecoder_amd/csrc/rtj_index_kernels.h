@@ -24,6 +24,7 @@
 
 #include "rtj_common.h"
 #include "rtj_decode_kernels.h"
+#include "rtj_walk_kernels.h"
 
 namespace mirtj {
 
@@ -154,12 +155,6 @@ __device__ __forceinline__ void summarize_chunk(const FrameDev* __restrict__ fra
   __shared__ __attribute__((aligned(16))) uint8_t s_nc[kTabN];         // ... or chroma
   __shared__ uint32_t s_wave[kSumThreads / 64];
   __shared__ uint32_t s_grp[12];
-#ifdef MIRTJ_SUM_NOALIAS
-  __shared__ uint16_t s_f[kChunk];
-  __shared__ uint16_t s_slot[2 * kEntries];
-  __shared__ uint16_t s_list[kEntries];
-  __shared__ uint32_t s_res[kEntries];
-#else
   // the sums and the bytes are dead once the lengths are known (step 3): their space is reused, which
   // brings the workgroup to 20 KB of LDS, i.e. up to eight workgroups per CU instead of five
   static_assert(kChunk <= kStageN && 2 * kEntries + kEntries + 2 * kEntries <= kStageN / 2, "aliased LDS layout");
@@ -167,7 +162,6 @@ __device__ __forceinline__ void summarize_chunk(const FrameDev* __restrict__ fra
   uint16_t* const s_slot = (uint16_t*)s_b4;                // first-hop targets: marker, then index into s_list
   uint16_t* const s_list = s_slot + 2 * kEntries;          // the distinct first-hop targets
   uint32_t* const s_res = (uint32_t*)(s_list + kEntries);  // (macroblocks << 16) | exit offset of each distinct target
-#endif
 
   const FrameDev f = frames[frame_index];
   const uint32_t c = blockIdx.x;

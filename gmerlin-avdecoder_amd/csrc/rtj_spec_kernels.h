@@ -34,6 +34,7 @@
 
 #include "rtj_common.h"
 #include "rtj_decode_kernels.h"
+#include "rtj_walk_kernels.h"
 
 #ifndef MIRTJ_SPEC_CHUNK
 #define MIRTJ_SPEC_CHUNK 2048
@@ -875,12 +876,6 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
         const uint32_t* const bits = br ? ra.runbits : recbits;
         const uint32_t wk = br ? br - 1u : R, tiles = br ? spec_run_tiles(ra.S) : (uint32_t)kSpecTilesMax;
         const uint32_t kend = br ? min(tiles * 4u, ((c0 + j + 1u) * (uint32_t)kSpecChunk - first_byte + 31u) >> 5) : tiles * 4u;
-#ifdef MIRTJ_EXP_VER_FROM_ZERO  // A/B (short leads only): every bit of the span, ranks counted from the walker's first byte
-        w0[u] = m[u] ? bits[spec_bits_dword_t(wk, (uint32_t)lane, tiles)] : 0u;
-        w1[u] = m[u] ? bits[spec_bits_dword_t(wk, (uint32_t)lane + 64u, tiles)] : 0u;
-        first[u] = c0 + j < nsc && c0 + j ? hand[sc0 + c0 + j].x >> 16 : 0u;
-        continue;
-#endif
         // dwords from the 16-byte piece that holds the hand-over point on: four lanes then read one piece (the pieces of
         // a walker lie 1 KB apart); started at the hand-over point's own dword, lane quads straddled two pieces and the
         // kernel took 2.04 ms per 16,384 pictures instead of 1.60 (profiles/r03/ab_verify_bit_addressing.txt)
@@ -898,11 +893,7 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
         const uint32_t tot0 = (uint32_t)__builtin_amdgcn_readlane((int)in0, 63);
         const uint32_t in1 = wave_incl_scan(c1_) + tot0;
         uint32_t* const o = out + base[u];
-#ifdef MIRTJ_EXP_VER_FROM_ZERO
-        const uint32_t q0 = 32u * (uint32_t)lane, q1 = q0 + 2048u;
-#else
         const uint32_t q0 = (first[u] & ~127u) + 32u * (uint32_t)lane, q1 = q0 + 2048u;  // walker-relative position of the dwords' first byte
-#endif
         // Ranks are scattered over the lanes (a lane owns the starts of its 32 bytes), the index wants them in order:
         // written straight to memory, a store instruction touched a dozen 64-byte pieces for 64 offsets and the kernel
         // took 2.1 ms per 16384 pictures.  The offsets are therefore put in rank order in LDS (scattered 16-bit writes
@@ -911,11 +902,7 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
         uint16_t* const sp = s_pos[wv];
         for (uint32_t r0 = 0; r0 < m[u]; r0 += (uint32_t)kSpecVerWindow) {
           const uint32_t span_ = min((uint32_t)kSpecVerWindow, m[u] - r0);
-#ifdef MIRTJ_EXP_VER_FROM_ZERO
-          int rk0 = (int)(in0 - c0_) - (int)first[u] - (int)r0, rk1 = (int)(in1 - c1_) - (int)first[u] - (int)r0;
-#else
           int rk0 = (int)(in0 - c0_) - (int)r0, rk1 = (int)(in1 - c1_) - (int)r0;
-#endif
           uint32_t m0 = w0[u], m1 = w1[u];
           // both dwords of a lane in one loop: it runs for the fullest dword of the wave (4-5 starts where a
           // macroblock's chroma blocks lie, 2 in luma), not for the sum of the two
@@ -958,7 +945,7 @@ __global__ __launch_bounds__(kSpecVerThreads) void k_spec_verify(const FrameDev*
 
 // A walker that had not fallen into step by the end of its lead is walked again, this time from a byte that is known
 // to start a (macro)block if its predecessor is right (the second k_spec_verify pass checks exactly that): one WAVE per
-// such walker, the block-by-block walker of rtj_decode_kernels.h (a lane-serial walker would take as long for one chunk
+// such walker, the block-by-block walker of rtj_walk_kernels.h (a lane-serial walker would take as long for one chunk
 // as k_spec_walk takes for all).  Content whose walks lock late — noise of +-24 and more at the highest quality —
 // needs two things round 2's repair did not do, and without them its packets were refused one and all:
 //   * walkers out of step that FOLLOW one another are one wave's job: the byte the second is to start from was read off

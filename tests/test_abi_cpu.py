@@ -71,3 +71,28 @@ def test_hand_issued_loads_of_k_decode_are_not_touched_before_their_wait(tmp_pat
         r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_async_loads.py"), str(asm)],
                            capture_output=True, text=True)
         assert r.returncode == 0, name + ": " + r.stdout + r.stderr
+
+
+# every MIRTJ_ name the kernel sources test in a preprocessor conditional: the size parameters a build may override,
+# and the two builds build.py knows besides the product.  A compile-time form switch is code that nothing builds or
+# tests; one that is added has to be added here, where someone reviews it.
+CONDITIONAL_NAMES = {
+    "MIRTJ_DEC_ITERS", "MIRTJ_DEC_WAVES", "MIRTJ_COEF_STRIDE", "MIRTJ_DEC_LDS_PAD", "MIRTJ_SPLIT_LUMA_SG",
+    "MIRTJ_NOP_ROW", "MIRTJ_NOP_COL", "MIRTJ_NOP_PX", "MIRTJ_NOP_LO3",
+    "MIRTJ_SPEC_CHUNK", "MIRTJ_SPEC_LEAD", "MIRTJ_SPEC_LEAD_LONG", "MIRTJ_SPEC_LEAD_VERY", "MIRTJ_SPEC_VER_THREADS",
+    "MIRTJ_SPEC_VER_BATCH",
+    "MIRTJ_SEARCH_UNROLL", "MIRTJ_F_CHAINS", "MIRTJ_SUM_WAVES", "MIRTJ_EMIT_THREADS",
+    "MIRTJ_TEST_GENERIC_PATHS", "MIRTJ_EXPERIMENTS",
+}
+
+
+def test_kernel_sources_test_no_macro_outside_the_reviewed_list():
+    csrc = os.path.join(ROOT, "gmerlin-avdecoder_amd", "csrc")
+    found = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".h", ".hip")):
+            continue
+        txt = open(os.path.join(csrc, f), errors="ignore").read().replace("\\\n", " ")
+        for line in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$", txt, re.M):
+            found |= set(re.findall(r"\bMIRTJ_\w+", line.split("//")[0]))
+    assert found == CONDITIONAL_NAMES, (sorted(found - CONDITIONAL_NAMES), sorted(CONDITIONAL_NAMES - found))

@@ -1,7 +1,7 @@
 """Static resource and instruction-class report of the compiled gfx950 kernels.
 
     python tools/isa_report.py [--unit rtjpeg|dv] [--kernel k_decode] [--cflags "..."] [--keep DIR] [--json] [--digest]
-                               [--src DIR] [--bodies FILE]
+                               [--opcodes] [--src DIR] [--bodies FILE]
 
 Compiles csrc/mi_rtjpeg.hip (--unit dv: csrc/mi_dv.hip) with -save-temps (device assembly) and prints, per kernel, what the
 code object's metadata says (VGPR / SGPR count, scalar-register spills, LDS bytes, scratch) and a
@@ -14,7 +14,8 @@ no label (assembler directives: .amdhsa_kernel <mangled name>, .section .text.<m
 are left out, so a kernel that is renamed or becomes a template instance keeps its hash when its code is the same; the
 register, spill, LDS and scratch figures come from the metadata and are printed beside the hash.  --src compiles another
 checkout's csrc/ (e.g. the parent commit's) with this tool; --bodies writes the hashed text of the selected kernels to a
-file, so that `diff` can compare two builds line by line."""
+file, so that `diff` can compare two builds line by line.  --opcodes adds a second hash, of the mnemonics and labels in
+order with the operands dropped: two builds that differ only in register numbering keep it."""
 import argparse
 import hashlib
 import json
@@ -125,8 +126,9 @@ def parse(path):
         # the kernel's mangled name and its descriptor, which the resource figures below report from the metadata
         body = [x for x in body if x and (not x.startswith(".") or x.endswith(":"))]
         digest = hashlib.sha1("\n".join(body).encode()).hexdigest()[:16]
+        opcodes = hashlib.sha1("\n".join(x.split()[0] for x in body).encode()).hexdigest()[:16]
         m = meta[k]
-        rep[k] = {"digest": digest, "body": body, "vgpr": int(m.get("vgpr_count", 0)), "sgpr": int(m.get("sgpr_count", 0)),
+        rep[k] = {"digest": digest, "opcodes": opcodes, "body": body, "vgpr": int(m.get("vgpr_count", 0)), "sgpr": int(m.get("sgpr_count", 0)),
                   "sgpr_spill": int(m.get("sgpr_spill_count", 0)), "vgpr_spill": int(m.get("vgpr_spill_count", 0)),
                   "lds_bytes": int(m.get("group_segment_fixed_size", 0)),
                   "scratch_bytes": int(m.get("private_segment_fixed_size", 0)), "static": c}
@@ -140,6 +142,7 @@ def main():
     ap.add_argument("--keep", default=None)
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--digest", action="store_true", help="print a hash of each kernel's instruction text")
+    ap.add_argument("--opcodes", action="store_true", help="print a hash of each kernel's mnemonics and labels, operands dropped")
     ap.add_argument("--src", default=CSRC, help="the csrc/ directory to compile")
     ap.add_argument("--unit", choices=sorted(UNITS), default="rtjpeg", help="which library's kernels")
     ap.add_argument("--bodies", default=None, help="write the selected kernels' instruction text (as hashed) to this file")
@@ -165,7 +168,8 @@ def main():
         print(f"{k}: vgpr {v['vgpr']} sgpr {v['sgpr']} sgpr_spill {v['sgpr_spill']} vgpr_spill {v['vgpr_spill']} "
               f"lds {v['lds_bytes']} scratch {v['scratch_bytes']} | valu {c['valu']} (readlane {c['v_readlane']} "
               f"writelane {c['v_writelane']}) salu {c['salu']} smem {c['smem']} lds {c['lds']} vmem {c['vmem']} "
-              f"waitcnt {c['waitcnt']} s_nop {c['s_nop']} branch {c['branch']}" + (f" | text {v['digest']}" if a.digest else ""))
+              f"waitcnt {c['waitcnt']} s_nop {c['s_nop']} branch {c['branch']}" + (f" | text {v['digest']}" if a.digest else "") +
+              (f" | opcodes {v['opcodes']}" if a.opcodes else ""))
 
 
 if __name__ == "__main__":
