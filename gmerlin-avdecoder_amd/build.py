@@ -83,6 +83,20 @@ def build_dv(force=False, verbose=False):
     return DV_LIB
 
 
+YUV_LIB = os.path.join(LIBDIR, "libmi_yuv.so")
+
+
+def build_yuv(force=False, verbose=False):
+    """libmi_yuv.so: the uncompressed QuickTime YUV family (include/mi_yuv.h), gfx950.  The rule is csrc/Makefile's."""
+    cmd = ["make", "-C", CSRC, "HIPCC=" + HIPCC, YUV_LIB] + (["-B"] if force else [])
+    if verbose:
+        print(" ".join(cmd))
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("make libmi_yuv.so failed:\n" + r.stdout + r.stderr)
+    return YUV_LIB
+
+
 TEST_VARIANT = os.path.join(LIBDIR, "libmi_rtjpeg_generic_paths.so")
 
 
@@ -128,5 +142,6 @@ def build_experiments(force=False):
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_dv(force="--force" in sys.argv, verbose=True))
+    print(build_yuv(force="--force" in sys.argv, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=True))
