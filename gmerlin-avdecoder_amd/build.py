@@ -68,7 +68,7 @@ DV_SOURCES = ["mi_dv.hip", "dv_tables.cpp"]
 
 def build_dv(force=False, verbose=False):
     """libmi_dv.so: the DV decoder and encoder, all five systems (include/mi_dv.h), gfx950."""
-    deps = glob.glob(os.path.join(CSRC, "dv_*.h")) + [os.path.join(CSRC, f) for f in DV_SOURCES + ["host_owned.h"]] + \
+    deps = glob.glob(os.path.join(CSRC, "dv_*.h")) + [os.path.join(CSRC, f) for f in DV_SOURCES + ["host_base.h"]] + \
            [os.path.join(HERE, "..", "include", "mi_dv.h")]
     if not force and os.path.exists(DV_LIB) and all(os.path.getmtime(f) <= os.path.getmtime(DV_LIB) for f in deps):
         return DV_LIB

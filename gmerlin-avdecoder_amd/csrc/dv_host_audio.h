@@ -31,12 +31,12 @@ int audio_batch(mi_dv_ctx* c, const Row& r, const char* who, const void* d_frame
   if (rc == MI_DV_OK) rc = k.apart(d_info, info_bytes, "d_info", d_frames, frame_bytes, "d_frames");
   if (rc == MI_DV_OK) rc = k.apart(d_info, info_bytes, "d_info", d_pcm, pcm_bytes, "d_pcm");
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   mi_dv_ctx::Audio& a = c->audio;
   rc = a.time.begin(c, c->stream);
   if (rc != MI_DV_OK) return rc;
   r.audio_extract(c->stream, (const uint8_t*)d_frames, (unsigned)n, (uint8_t*)d_pcm, (uint32_t)pairs, (int32_t*)d_info, a.d_tab);
-  DVCHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   return a.time.end(c, c->stream);
 }
 
@@ -63,23 +63,23 @@ int audio_write_batch(mi_dv_ctx* c, const Row& r, const char* who, void* d_frame
   if (rc == MI_DV_OK)
     rc = k.apart(d_pcm, (size_t)n * pairs * MI_DV_AUDIO_PAIR_BYTES, "d_pcm", d_frames, (size_t)n * r.frame_bytes, "d_frames");
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   mi_dv_ctx::Audio& a = c->audio;
-  if (!a.samples_done) DVCHK(c, hipEventCreateWithFlags(&a.samples_done.p, hipEventDisableTiming));
+  if (!a.samples_done) HIPCHK(c, hipEventCreateWithFlags(&a.samples_done.p, hipEventDisableTiming));
   if ((uint64_t)n > a.d_samples.cap) {
     rc = release_together(c, c->stream, a.h_samples, a.d_samples);
     if (rc == MI_DV_OK) rc = a.h_samples.grow(c, (uint64_t)n, nullptr);
     if (rc == MI_DV_OK) rc = a.d_samples.grow(c, (uint64_t)n, nullptr);
     if (rc != MI_DV_OK) return rc;
   }
-  DVCHK(c, hipEventSynchronize(a.samples_done));  // (the last upload has left the pinned buffer; at once if there was none)
+  HIPCHK(c, hipEventSynchronize(a.samples_done));  // (the last upload has left the pinned buffer; at once if there was none)
   for (int i = 0; i < n; i++) a.h_samples[i] = samples[i];
-  DVCHK(c, hipMemcpyAsync(a.d_samples, a.h_samples, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  DVCHK(c, hipEventRecord(a.samples_done, c->stream));
+  HIPCHK(c, hipMemcpyAsync(a.d_samples, a.h_samples, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(a.samples_done, c->stream));
   rc = a.time.begin(c, c->stream);
   if (rc != MI_DV_OK) return rc;
   r.audio_write(c->stream, (uint8_t*)d_frames, (unsigned)n, (const uint8_t*)d_pcm, (uint32_t)pairs, (uint32_t)freq, a.d_samples, a.d_tab);
-  DVCHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   return a.time.end(c, c->stream);
 }
 }  // namespace

@@ -17,12 +17,12 @@ int encode_batch(mi_dv_ctx* c, const Row& r, const char* who, const void* d_pics
   if (rc == MI_DV_OK) rc = k.aligned(d_frames, d_pics, nullptr, "4-byte and d_pics 8-byte");
   if (rc == MI_DV_OK) rc = k.apart(d_frames, (size_t)n * r.frame_bytes, "d_frames", d_pics, (size_t)n * r.pic_bytes, "d_pics");
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipSetDevice(c->device));
-  DVCHK(c, hipMemsetAsync(c->d_enc_stats, 0, kEncStats * sizeof(unsigned long long), c->stream));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemsetAsync(c->d_enc_stats, 0, kEncStats * sizeof(unsigned long long), c->stream));
   rc = c->encode_time.begin(c, c->stream);
   if (rc != MI_DV_OK) return rc;
   r.encode(c->stream, (const uint8_t*)d_pics, (unsigned)n, (uint8_t*)d_frames, c->d_enc, (uint32_t)flags, c->d_enc_stats);
-  DVCHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   return c->encode_time.end(c, c->stream);
 }
 
@@ -35,16 +35,16 @@ int encode_one(mi_dv_ctx* c, const Row& r, const char* who, const uint8_t* const
   int rc = check_flags(c, who, flags);
   if (rc == MI_DV_OK) rc = check_strides(c, r, strides);
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   rc = one_frame_buffers(c, r);
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipStreamSynchronize(c->stream));  // (the pinned picture is free)
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // (the pinned picture is free)
   copy_planes(r, c->h_pic, (uint8_t* const*)planes, strides, false);  // (read only)
-  DVCHK(c, hipMemcpyAsync(c->d_pic, c->h_pic, (size_t)r.pic_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_pic, c->h_pic, (size_t)r.pic_bytes, hipMemcpyHostToDevice, c->stream));
   rc = encode_batch(c, r, who, c->d_pic, 1, c->d_frame, flags);
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipMemcpyAsync(frame, c->d_frame, (size_t)r.frame_bytes, hipMemcpyDeviceToHost, c->stream));
-  DVCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(frame, c->d_frame, (size_t)r.frame_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return MI_DV_OK;
 }
 }  // namespace

@@ -12,7 +12,7 @@ int hold_buffers(mi_dv_ctx* c, size_t desc, size_t rows) {
   mi_dv_ctx::Hold& h = c->hold;
   int rc = h.d_held.grow(c, (uint64_t)kHoldCounters * kHoldCounterStride, nullptr);
   if (rc != MI_DV_OK) return rc;
-  if (!h.desc_done) DVCHK(c, hipEventCreateWithFlags(&h.desc_done.p, hipEventDisableTiming));
+  if (!h.desc_done) HIPCHK(c, hipEventCreateWithFlags(&h.desc_done.p, hipEventDisableTiming));
   if (desc > h.d_desc.cap) {  // (the last of the two to grow)
     rc = release_together(c, c->stream, h.h_desc, h.d_desc);
     if (rc == MI_DV_OK) rc = h.h_desc.grow(c, desc, nullptr);
@@ -55,7 +55,7 @@ int decode_held(mi_dv_ctx* c, const Row& r, const char* who, const void* d_frame
   if (rc != MI_DV_OK) return rc;
   if (!c) return fail(c, MI_DV_ERR_ARG, "%s: NULL instance", who);
   if (!sta_mask) sta_mask = MI_DV_STA_ERRORS;
-  DVCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   mi_dv_ctx::Hold& h = c->hold;
   // a run has a source when it has an earlier picture of its own or one of d_prev
   std::vector<HoldChunkDev> chunks;
@@ -79,11 +79,11 @@ int decode_held(mi_dv_ctx* c, const Row& r, const char* who, const void* d_frame
   if (rc != MI_DV_OK) return rc;
   h.counted = false;
   if (chunks.empty()) return MI_DV_OK;
-  DVCHK(c, hipEventSynchronize(h.desc_done));  // (the last upload has left the pinned buffer; at once if there was none)
+  HIPCHK(c, hipEventSynchronize(h.desc_done));  // (the last upload has left the pinned buffer; at once if there was none)
   memcpy(h.h_desc, chunks.data(), chunk_bytes);
   memcpy(h.h_desc + chunk_bytes, runs.data(), run_bytes);
-  DVCHK(c, hipMemcpyAsync(h.d_desc, h.h_desc, chunk_bytes + run_bytes, hipMemcpyHostToDevice, c->stream));
-  DVCHK(c, hipEventRecord(h.desc_done, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h.d_desc, h.h_desc, chunk_bytes + run_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(h.desc_done, c->stream));
   const HoldChunkDev* d_chunks = (const HoldChunkDev*)h.d_desc.p;
   const HoldRunDev* d_runs = (const HoldRunDev*)(h.d_desc + chunk_bytes);
   const uint32_t nchunks = (uint32_t)chunks.size(), nruns = (uint32_t)runs.size(), nmb = (uint32_t)r.nmb;
@@ -95,7 +95,7 @@ int decode_held(mi_dv_ctx* c, const Row& r, const char* who, const void* d_frame
   hipLaunchKernelGGL(k_dv_hold_carry, dim3(gx, nruns < kHoldMaxGridY ? nruns : kHoldMaxGridY), dim3(kHoldScanThreads), 0, c->stream,
                      d_runs, nruns, d_chunks, nmb, (const uint64_t*)h.d_mask.p, h.d_carry.p, h.d_held.p);
   r.hold_copy(c->stream, d_chunks, nchunks * (uint32_t)kHoldSubs, h.d_mask, h.d_carry, (uint8_t*)d_pics, (const uint8_t*)d_prev, h.d_held);
-  DVCHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   rc = h.time.end(c, c->stream);
   h.counted = rc == MI_DV_OK;
   return rc;
@@ -103,13 +103,13 @@ int decode_held(mi_dv_ctx* c, const Row& r, const char* who, const void* d_frame
 
 // the macroblocks the last held batch took from another picture; synchronises
 int hold_count(mi_dv_ctx* c, long long* held) {
-  DVCHK(c, hipSetDevice(c->device));
-  DVCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   unsigned long long v = 0;
   if (c->hold.counted) {  // the partial counts (dv_hold_kernels.h: kHoldCounters)
     std::vector<unsigned long long> part((size_t)kHoldCounters * kHoldCounterStride);
-    DVCHK(c, hipMemcpyAsync(part.data(), c->hold.d_held, part.size() * sizeof part[0], hipMemcpyDeviceToHost, c->stream));
-    DVCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(part.data(), c->hold.d_held, part.size() * sizeof part[0], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < kHoldCounters; i++) v += part[(size_t)i * kHoldCounterStride];
   }
   *held = (long long)v;
@@ -132,14 +132,14 @@ int decode_one_held(mi_dv_ctx* c, const Row* r, int system, const uint8_t* frame
   const int at = (int)(r - kSystems);
   const bool had = h.kept == at;
   hold_forget(c);  // (until this frame's picture is there; a picture of another system is no source for a later frame)
-  DVCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   rc = one_frame_buffers(c, *r);
   for (DevBuf<uint8_t>& d : h.keep[at])
     if (rc == MI_DV_OK) rc = d.grow(c, (uint64_t)r->pic_bytes, nullptr);
   if (rc != MI_DV_OK) return rc;
   uint8_t* const last = h.keep[at][h.cur[at]];
   uint8_t* const now = h.keep[at][h.cur[at] ^ 1];
-  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, (size_t)r->frame_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_frame, frame, (size_t)r->frame_bytes, hipMemcpyHostToDevice, c->stream));
   rc = decode_held(c, *r, who, c->d_frame, 1, now, 0, nullptr, had ? last : nullptr, sta_mask);
   if (rc != MI_DV_OK) return rc;
   rc = planes_out(c, *r, now, planes, strides);

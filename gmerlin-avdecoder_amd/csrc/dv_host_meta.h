@@ -16,11 +16,11 @@ int meta_batch(mi_dv_ctx* c, const Row& r, const char* who, const void* d_frames
   if (rc == MI_DV_OK)
     rc = k.apart(d_meta, (size_t)n * kMetaInts * sizeof(int32_t), "d_meta", d_frames, (size_t)n * r.frame_bytes, "d_frames");
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   rc = c->meta.time.begin(c, c->stream);
   if (rc != MI_DV_OK) return rc;
   r.meta_extract(c->stream, (const uint8_t*)d_frames, (unsigned)n, (int32_t*)d_meta);
-  DVCHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   return c->meta.time.end(c, c->stream);
 }
 
@@ -46,12 +46,12 @@ int meta_write_batch(mi_dv_ctx* c, const Row& r, const char* who, void* d_frames
     return fail(c, MI_DV_ERR_ARG, "%s: recording time %lld s; below %lld (2070), or negative for none", who, rec_seconds,
                 (long long)kMetaLastSecond);
   if (wide != 0 && wide != 1) return fail(c, MI_DV_ERR_ARG, "%s: wide %d; 0 or 1", who, wide);
-  DVCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   rc = c->meta.time.begin(c, c->stream);
   if (rc != MI_DV_OK) return rc;
   r.meta_write(c->stream, (uint8_t*)d_frames, (unsigned)n, (unsigned long long)first_frame, (uint32_t)drop_frame,
                rec_seconds < 0 ? -1ll : rec_seconds, (uint32_t)wide);
-  DVCHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   return c->meta.time.end(c, c->stream);
 }
 }  // namespace

@@ -2,13 +2,10 @@
 // the checks of a resident batch, the decode launch, the one-frame path.  Included by mi_dv.hip; not a kernel header.
 // (The held calls, the encoder, the sound and the timecode have headers of their own behind this one.)
 #pragma once
-#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
 #include <iterator>
-#include <mutex>
-#include <string>
 
 #include "dv_common.h"
 #include "dv_decode_kernels.h"
@@ -16,7 +13,8 @@
 #include "dv_encode_kernels.h"
 #include "dv_audio_kernels.h"
 #include "dv_meta_kernels.h"
-#include "dv_host_buf.h"
+#include "../../include/mi_dv.h"
+#include "host_base.h"
 
 using namespace midv;
 
@@ -136,12 +134,10 @@ int classify(const uint8_t* frame, size_t len) {
 }
 }  // namespace
 
-// ---- the instance.  Members are destroyed last to first: every buffer and event before the stream.  (Hidden: the
-// library exports the C ABI, not this struct's constructor and destructor) ----
-struct __attribute__((visibility("hidden"))) mi_dv_ctx {
-  int device = 0;
-  Stream stream;
-  std::string err;
+// ---- the instance: device, stream and error text are HostCtx's (host_base.h), destroyed after everything here.  The
+// timers go before the pool they hand their pairs to.  (Hidden: the library exports the C ABI, not this struct's
+// constructor and destructor) ----
+struct __attribute__((visibility("hidden"))) mi_dv_ctx : HostCtx {
   EventPool ev_free;
   DevBuf<Tables> d_tab;
   Timer decode_time{ev_free};  // k_dv_decode (mi_dv_kernel_times)
@@ -187,23 +183,6 @@ struct __attribute__((visibility("hidden"))) mi_dv_ctx {
 };
 
 namespace {
-std::mutex g_mu;
-std::string g_err;
-
-int fail(mi_dv_ctx* c, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (c) c->err = buf;
-  else {
-    std::lock_guard<std::mutex> l(g_mu);
-    g_err = buf;
-  }
-  return code;
-}
-
 // ---- a resident batch, checked.  Every entry point makes these checks in this order, with its own between them ----
 struct BatchCheck {
   mi_dv_ctx* c;
@@ -239,7 +218,7 @@ int decode_run(mi_dv_ctx* c, const Row& r, const void* d_frames, int n, void* d_
   int rc = c->decode_time.begin(c, c->stream);
   if (rc != MI_DV_OK) return rc;
   r.decode(c->stream, (const uint8_t*)d_frames, (unsigned)n, (uint8_t*)d_pics, c->d_tab);
-  DVCHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   return c->decode_time.end(c, c->stream);
 }
 int decode_batch(mi_dv_ctx* c, const Row& r, const char* who, const void* d_frames, int n, void* d_pics) {
@@ -247,7 +226,7 @@ int decode_batch(mi_dv_ctx* c, const Row& r, const char* who, const void* d_fram
   int rc = k.count(c && d_frames && d_pics, n, "frames");
   if (rc == MI_DV_OK) rc = k.aligned(d_frames, d_pics, nullptr, "4-byte and d_pics 8-byte");
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   return decode_run(c, r, d_frames, n, d_pics);
 }
 
@@ -301,8 +280,8 @@ int check_one(mi_dv_ctx* c, const Row& r, const char* who, const uint8_t* frame,
 
 // the device picture d_pic of system r through the pinned buffer into the caller's planes; synchronises
 int planes_out(mi_dv_ctx* c, const Row& r, const uint8_t* d_pic, uint8_t* const planes[3], const int strides[3]) {
-  DVCHK(c, hipMemcpyAsync(c->h_pic, d_pic, (size_t)r.pic_bytes, hipMemcpyDeviceToHost, c->stream));
-  DVCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pic, d_pic, (size_t)r.pic_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   copy_planes(r, c->h_pic, planes, strides, true);
   return MI_DV_OK;
 }
@@ -312,23 +291,12 @@ int decode_one(mi_dv_ctx* c, const Row& r, const char* who, const uint8_t* frame
                const int strides[3]) {
   int rc = check_one(c, r, who, frame, len, planes, strides);
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   rc = one_frame_buffers(c, r);
   if (rc != MI_DV_OK) return rc;
-  DVCHK(c, hipMemcpyAsync(c->d_frame, frame, (size_t)r.frame_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_frame, frame, (size_t)r.frame_bytes, hipMemcpyHostToDevice, c->stream));
   rc = decode_batch(c, r, who, c->d_frame, 1, c->d_pic);
   if (rc != MI_DV_OK) return rc;
   return planes_out(c, r, c->d_pic, planes, strides);
-}
-
-// the body of the mi_dv_*_times: waits for the stream, then the timer's sum and `per_pair` launches a pair
-int times(mi_dv_ctx* c, Timer* t, int per_pair, float* total_ms, int* launches) {
-  if (!c || !total_ms || !launches) return MI_DV_ERR_ARG;
-  DVCHK(c, hipSetDevice(c->device));
-  DVCHK(c, hipStreamSynchronize(c->stream));
-  int pairs = 0;
-  const int rc = t->collect(c, total_ms, &pairs);
-  if (rc == MI_DV_OK) *launches = per_pair * pairs;
-  return rc;
 }
 }  // namespace

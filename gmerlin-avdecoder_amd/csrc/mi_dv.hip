@@ -1,8 +1,9 @@
 // mi_dv.hip — C ABI (include/mi_dv.h) of the MI355X DV decoder and encoder (25 Mbit/s: 525/60 4:1:1, 625/50 4:2:0, 625/50 4:1:1;
 // 50 Mbit/s: both line systems in 4:2:2).  No CPU path: without a gfx950 device every call fails with a message.
-// The entry points only; what they call: dv_host_buf.h (owned buffers, the timer), dv_host_systems.h (the table of
-// systems, the instance, the decoder), dv_host_hold.h (the held calls), dv_host_encode.h (the encoder),
-// dv_host_audio.h (the sound), dv_host_meta.h (timecode, recording date and time, aspect).
+// The entry points only; what they call: host_base.h (shared with the other device libraries: owned buffers, errors, the
+// timer, the bodies of the calls every library has), dv_host_systems.h (the table of systems, the instance, the
+// decoder), dv_host_hold.h (the held calls), dv_host_encode.h (the encoder), dv_host_audio.h (the sound),
+// dv_host_meta.h (timecode, recording date and time, aspect).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -30,40 +31,16 @@ static_assert(kAgrees<Sys625_422, MI_DV_SYS_625_50_422, MI_DV_625_422_FRAME_BYTE
 static_assert(MI_DV_SYS_525_60_422 == (0x4 | 0) && MI_DV_SYS_625_50_422 == (0x4 | 1), "4:2:2 system = stype | DSF");
 static_assert(kSystems[0].id == MI_DV_SYS_525_60, "mi_dv_decode_batch and mi_dv_decode_frame take the table's first row");
 
-namespace {
-bool is_gfx950(int dev) {
-  hipDeviceProp_t p;
-  return hipGetDeviceProperties(&p, dev) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0;
-}
-}  // namespace
+static_assert(MI_DV_OK == kOk && MI_DV_ERR_HIP == kErrHip, "header and host base agree");
 
 extern "C" {
 
-int mi_dv_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  int ok = 0;
-  for (int i = 0; i < n; i++) ok += is_gfx950(i);
-  return ok;
-}
+int mi_dv_device_count(void) { return device_count(); }
 
-const char* mi_dv_last_error(const mi_dv_ctx* c) {
-  if (c) return c->err.c_str();
-  std::lock_guard<std::mutex> l(g_mu);
-  return g_err.c_str();
-}
+const char* mi_dv_last_error(const mi_dv_ctx* c) { return last_error(c); }
 
 mi_dv_ctx* mi_dv_create(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-    fail(nullptr, MI_DV_ERR_HIP, "no HIP device: the DV decoder has no CPU path");
-    return nullptr;
-  }
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= n || !is_gfx950(device)) {
-    fail(nullptr, MI_DV_ERR_ARG, "device %d is not a gfx950 (MI355X) device", device);
-    return nullptr;
-  }
+  if ((device = usable_device(device, "DV decoder", MI_DV_ERR_ARG)) < 0) return nullptr;
   Tables t;
   if (!build_tables(&t)) {
     fail(nullptr, MI_DV_ERR_ARG, "internal: the variable-length code's tables are inconsistent");
@@ -95,7 +72,7 @@ void mi_dv_destroy(mi_dv_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  delete c;  // (buffers and events, then the stream: the order of mi_dv_ctx's members)
+  delete c;  // (buffers and events, then HostCtx's stream)
 }
 
 void* mi_dv_dev_alloc(mi_dv_ctx* c, size_t bytes) {
@@ -107,32 +84,16 @@ void* mi_dv_dev_alloc(mi_dv_ctx* c, size_t bytes) {
   }
   return d;
 }
-void mi_dv_dev_free(mi_dv_ctx* c, void* d) {
-  if (!c || !d) return;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-}
+void mi_dv_dev_free(mi_dv_ctx* c, void* d) { dev_free(c, d); }
 int mi_dv_h2d(mi_dv_ctx* c, void* d, const void* h, size_t n) {
   if (!c || (!d && n) || (!h && n)) return fail(c, MI_DV_ERR_ARG, "mi_dv_h2d: NULL argument");
-  DVCHK(c, hipSetDevice(c->device));
-  DVCHK(c, hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, c->stream));
-  DVCHK(c, hipStreamSynchronize(c->stream));
-  return MI_DV_OK;
+  return copy_sync(c, d, h, n, hipMemcpyHostToDevice);
 }
 int mi_dv_d2h(mi_dv_ctx* c, void* h, const void* d, size_t n) {
   if (!c || (!d && n) || (!h && n)) return fail(c, MI_DV_ERR_ARG, "mi_dv_d2h: NULL argument");
-  DVCHK(c, hipSetDevice(c->device));
-  DVCHK(c, hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, c->stream));
-  DVCHK(c, hipStreamSynchronize(c->stream));
-  return MI_DV_OK;
+  return copy_sync(c, h, d, n, hipMemcpyDeviceToHost);
 }
-int mi_dv_sync(mi_dv_ctx* c) {
-  if (!c) return MI_DV_ERR_ARG;
-  DVCHK(c, hipSetDevice(c->device));
-  DVCHK(c, hipStreamSynchronize(c->stream));
-  return MI_DV_OK;
-}
+int mi_dv_sync(mi_dv_ctx* c) { return c ? stream_sync(c) : MI_DV_ERR_ARG; }
 
 #ifdef MIDV_DEBUG
 void mi_dv_debug_buffer(void* d) { g_dbg = d; }
@@ -149,7 +110,7 @@ int mi_dv_decode_batch_sys(mi_dv_ctx* c, int system, const void* d_frames, int n
 }
 
 int mi_dv_kernel_times(mi_dv_ctx* c, float* total_ms, int* launches) {
-  return times(c, c ? &c->decode_time : nullptr, 1, total_ms, launches);
+  return times(c, c ? &c->decode_time : nullptr, 1, total_ms, launches, MI_DV_ERR_ARG);
 }
 
 size_t mi_dv_copy_tables(void* out, size_t cap) {
@@ -238,7 +199,7 @@ int mi_dv_hold_stats(mi_dv_ctx* c, long long* held) {
 }
 
 int mi_dv_hold_times(mi_dv_ctx* c, float* total_ms, int* launches) {  // k_dv_hold_mask, k_dv_hold_carry, k_dv_hold_copy
-  return times(c, c ? &c->hold.time : nullptr, 3, total_ms, launches);
+  return times(c, c ? &c->hold.time : nullptr, 3, total_ms, launches, MI_DV_ERR_ARG);
 }
 
 int mi_dv_hold_reset(mi_dv_ctx* c) {
@@ -268,16 +229,16 @@ int mi_dv_encode_frame(mi_dv_ctx* c, int system, const uint8_t* const planes[3],
 }
 
 int mi_dv_encode_times(mi_dv_ctx* c, float* total_ms, int* launches) {
-  return times(c, c ? &c->encode_time : nullptr, 1, total_ms, launches);
+  return times(c, c ? &c->encode_time : nullptr, 1, total_ms, launches, MI_DV_ERR_ARG);
 }
 
 int mi_dv_encode_stats(mi_dv_ctx* c, long long qno_hist[16], long long* dropped) {
   if (!c || !qno_hist || !dropped) return MI_DV_ERR_ARG;
-  DVCHK(c, hipSetDevice(c->device));
-  DVCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   unsigned long long v[kEncStats];
-  DVCHK(c, hipMemcpyAsync(v, c->d_enc_stats, sizeof v, hipMemcpyDeviceToHost, c->stream));
-  DVCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(v, c->d_enc_stats, sizeof v, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < 16; i++) qno_hist[i] = (long long)v[i];
   *dropped = (long long)v[16];
   return MI_DV_OK;
@@ -306,7 +267,7 @@ int mi_dv_audio_samples(int system, int samplerate, long long frame) {
 }
 
 int mi_dv_audio_times(mi_dv_ctx* c, float* total_ms, int* launches) {  // k_dv_audio_extract, k_dv_audio_write
-  return times(c, c ? &c->audio.time : nullptr, 1, total_ms, launches);
+  return times(c, c ? &c->audio.time : nullptr, 1, total_ms, launches, MI_DV_ERR_ARG);
 }
 
 size_t mi_dv_audio_copy_tables(void* out, size_t cap) {
@@ -344,7 +305,7 @@ int mi_dv_timecode_of(int system, long long frame, int drop_frame, int hmsf[4]) 
 }
 
 int mi_dv_meta_times(mi_dv_ctx* c, float* total_ms, int* launches) {  // k_dv_meta_extract, k_dv_meta_write
-  return times(c, c ? &c->meta.time : nullptr, 1, total_ms, launches);
+  return times(c, c ? &c->meta.time : nullptr, 1, total_ms, launches, MI_DV_ERR_ARG);
 }
 
 }  // extern "C"

@@ -2,11 +2,12 @@
 // gfx950 kernels.  No CPU decode path exists here: without a usable device every entry point
 // fails and reports why.
 //
-// This file: the instance's and a plan's state, plan_launch() and the plan entry points.  The rest of the host layer is
-// in the rtj_host_*.h headers it includes: owned buffers (rtj_host_buf.h), the environment switches (rtj_host_switches.h),
-// the stages of a launch (rtj_host_stages.h), sessions (rtj_host_pipe.h), encoder and colour stage (rtj_host_encode.h).
+// This file: the instance's and a plan's state, plan_launch() and the plan entry points.  The rest of the host layer:
+// host_base.h (shared with the other device libraries: owned buffers, streams and events, errors, the bodies of the calls
+// every library has), and the rtj_host_*.h headers: pinned memory with flags (rtj_host_buf.h), the environment switches
+// (rtj_host_switches.h), the stages of a launch (rtj_host_stages.h), sessions (rtj_host_pipe.h), encoder and colour
+// stage (rtj_host_encode.h).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -43,12 +44,12 @@ constexpr size_t kAllocPad = 256;  // kernels may read a few bytes past a packet
 constexpr int kMaxPlanFrames = 65535;       // a plan's frames are the y dimension of every grid
 constexpr uint64_t kOverlapMaxGroups = 8192ull * 255ull;  // plans from this many macroblock groups on run their kernels back to back
 
-std::mutex g_err_mu;
-std::string g_create_err = "";
+static_assert(MI_RTJ_OK == kOk && MI_RTJ_ERR_HIP == kErrHip, "header and host base agree");
 
+// a kernel's start and end while profiling: handles of events the plan owns (mi_rtj_plan::timing); `a` is the previous
+// kernel's `b` where kernels run back to back on one stream
 struct Timed {
   hipEvent_t a = nullptr, b = nullptr;
-  bool owns_a = true;  // false: `a` is the previous kernel's `b` (kernels run back to back on one stream)
 };
 
 // The three picture formats, one row each, indexed by MI_RTJ_FMT_*: the numbers are FmtShape's (rtj_common.h), the
@@ -146,7 +147,7 @@ struct SplitLists {
   // kernel is not enqueued at all (it would return at once: ~90 us of empty workgroups per 16,384 pictures) and
   // k_decode_split is told to run whatever the device's word says — so a stale view costs time on content that just
   // turned noisy, never pictures
-  PinnedBuf<uint32_t> h_mode_seen;
+  FlagPinnedBuf<uint32_t> h_mode_seen;
   uint32_t* d_mode_seen = nullptr;  // the same word, as the device addresses it
   int flip = 0;
 };
@@ -165,25 +166,20 @@ struct Overlap {
   // a plan that may (dyn) run like an overlapped plan's; the second index and the stream are made with the plan.
   bool dyn = false;
   bool last_overlapped = false;  // the launch before this one ran its index on own_idx
-  hipStream_t own_idx = nullptr;
+  // (members are destroyed last to first: the events and the second index before the stream, which is waited for first)
+  Stream own_idx;
   DevBuf<uint32_t> blkoff_b;     // the second block-offset index (the plan's blkoff is the first)
-  hipEvent_t e_read[2] = {nullptr, nullptr};
-  hipEvent_t e_idx = nullptr;    // index done (used whenever the index kernels have a stream of their own)
+  Event e_read[2];
+  Event e_idx;                   // index done (used whenever the index kernels have a stream of their own)
   int flip = 0;                  // which index the NEXT launch writes
   int last = 0;                  // which one the last launch wrote (mi_rtj_plan_read_index)
 
   void drop_stream() {
-    if (own_idx) {
-      (void)hipStreamSynchronize(own_idx);
-      (void)hipStreamDestroy(own_idx);
-    }
-    own_idx = nullptr;
+    if (own_idx) (void)hipStreamSynchronize(own_idx);
+    own_idx.release();
   }
   ~Overlap() {
-    if (e_idx) (void)hipEventDestroy(e_idx);
-    drop_stream();
-    for (hipEvent_t e : e_read)
-      if (e) (void)hipEventDestroy(e);
+    if (own_idx) (void)hipStreamSynchronize(own_idx);
   }
 };
 
@@ -202,12 +198,11 @@ struct Runs {
 
 }  // namespace
 
-struct mi_rtj_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
+// Device, stream and error text are HostCtx's (host_base.h), destroyed after everything here: buffers and e_input go
+// before the stream.
+struct mi_rtj_ctx : HostCtx {
   DevBuf<QTab> d_lut;
   uint8_t b8[kNumQTab][2] = {};  // host copy of (lb8, cb8) per LUT row
-  std::string err;
   // RTjpeg_t's header-driven state (lib/RTjpeg.c:3568-3579)
   int width = 0, height = 0, Q = 0;
   // which arm of RTjpeg_decompress's switch the instance decodes (RTjpeg_set_format, lib/RTjpeg.c:2421): MI_RTJ_FMT_*.
@@ -222,7 +217,7 @@ struct mi_rtj_ctx {
   // read on their own stream: the next launch of a plan with an index stream makes that stream wait for this event once
   // (not at every launch — that would put the index of launch k + 1 behind the transform of launch k)
   bool input_dirty = false;
-  hipEvent_t e_input = nullptr;
+  Event e_input;
 };
 
 struct mi_rtj_plan {
@@ -249,30 +244,11 @@ struct mi_rtj_plan {
   Overlap ov;                       // (declared behind the buffers: its stream is waited for before any of them is freed)
   std::vector<Timed> ev[MI_RTJ_NUM_KERNELS];  // one pair per launch while profiling
   std::vector<Timed> run_ev;        // while profiling: one per launch (b == nullptr: no phase 2 in it)
+  std::vector<Event> timing;        // the events ev and run_ev name (behind ov: they go before its stream)
   int launches = 0;
 };
 
 namespace {
-
-int fail(mi_rtj_ctx* c, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (c) c->err = buf;
-  else {
-    std::lock_guard<std::mutex> l(g_err_mu);
-    g_create_err = buf;
-  }
-  return code;
-}
-
-bool device_is_gfx950(int dev) {
-  hipDeviceProp_t p;
-  if (hipGetDeviceProperties(&p, dev) != hipSuccess) return false;
-  return strncmp(p.gcnArchName, "gfx950", 6) == 0;
-}
 
 // RTjpeg_decompress's header handling (lib/RTjpeg.c:3568-3579) on the instance state.
 // Returns the LUT row to use, or a negative error.
@@ -357,10 +333,10 @@ int plan_alloc_chunks(mi_rtj_plan* p) {
   }
   ChunkIndex& ch = p->chunk;
   int rc;  // (MI_RTJ_OK is 0: the first step of a chain that fails ends it)
-  if (chunks > ch.chunks() && ((rc = dev_release(c, s, ch.summary, ch.lentab)) || (rc = ch.summary.grow(c, kEntries * chunks, s)) ||
+  if (chunks > ch.chunks() && ((rc = release_together(c, s, ch.summary, ch.lentab)) || (rc = ch.summary.grow(c, kEntries * chunks, s)) ||
                                (rc = ch.lentab.grow(c, kChunk * chunks, s, 64))))
     return rc;
-  if (entries > ch.entries() && ((rc = dev_release(c, s, ch.pos, ch.mb)) || (rc = ch.pos.grow(c, entries, s)) || (rc = ch.mb.grow(c, entries, s))))
+  if (entries > ch.entries() && ((rc = release_together(c, s, ch.pos, ch.mb)) || (rc = ch.pos.grow(c, entries, s)) || (rc = ch.mb.grow(c, entries, s))))
     return rc;
   // ---- speculative index: worth it once the batch fills the device (a walker is one lane and runs
   //      for ~0.25 ms whatever the batch; a single packet is indexed faster by the exact kernels) ----
@@ -401,13 +377,13 @@ int plan_alloc_chunks(mi_rtj_plan* p) {
   // (rec: whole waves of walkers, + a spare walker for idle lanes; flag: the walkers zero [0, n) per launch; nfix and, below,
   // state are made once; ok starts as "nothing proven yet" for mi_rtj_plan_spec_stats)
   if (sp.n > sp.walkers_cap() &&
-      ((rc = dev_release(c, s, sp.chunks, sp.rec, sp.nrec, sp.wstart, sp.hand, sp.fix, sp.flag)) || (rc = sp.chunks.grow(c, sp.n, s)) ||
+      ((rc = release_together(c, s, sp.chunks, sp.rec, sp.nrec, sp.wstart, sp.hand, sp.fix, sp.flag)) || (rc = sp.chunks.grow(c, sp.n, s)) ||
        (rc = sp.rec.grow(c, spec_bits_words(sp.n), s)) || (rc = sp.nrec.grow(c, sp.n, s)) || (rc = sp.wstart.grow(c, sp.n, s)) ||
        (rc = sp.hand.grow(c, sp.n, s)) || (rc = sp.fix.grow(c, sp.n, s)) || (rc = sp.flag.grow(c, sp.n, s, 64, true)) ||
        (rc = sp.nfix.grow(c, 1, s, 0, true))))
     return rc;
   if (frames > sp.frames_cap()) {
-    if ((rc = dev_release(c, s, sp.base, sp.ok, sp.todo)) || (rc = sp.base.grow(c, frames + 1, s)) || (rc = sp.ok.grow(c, frames, s, 0, true)) ||
+    if ((rc = release_together(c, s, sp.base, sp.ok, sp.todo)) || (rc = sp.base.grow(c, frames + 1, s)) || (rc = sp.ok.grow(c, frames, s, 0, true)) ||
         (rc = sp.todo.grow(c, frames + 2, s)))
       return rc;
     HIPCHK(c, hipMemsetAsync(sp.todo + frames + 1, 0, sizeof(uint32_t), s));
@@ -415,10 +391,10 @@ int plan_alloc_chunks(mi_rtj_plan* p) {
   }
   if (sp.run_s > 1u) {
     const uint64_t words = spec_bits_words_t(sp.nruns, spec_run_tiles(sp.run_s));
-    if ((sp.nruns > sp.runs.cap && ((rc = dev_release(c, s, sp.runs)) || (rc = sp.runs.grow(c, sp.nruns, s)))) ||
-        (words > sp.runrec.cap && ((rc = dev_release(c, s, sp.runrec)) || (rc = sp.runrec.grow(c, words, s)))) ||
-        (sp.n > sp.brow.cap && ((rc = dev_release(c, s, sp.brow)) || (rc = sp.brow.grow(c, sp.n, s)))) ||
-        (sp.h_rbase.size() > sp.rbase.cap && ((rc = dev_release(c, s, sp.rbase)) || (rc = sp.rbase.grow(c, sp.h_rbase.size(), s)))))
+    if ((sp.nruns > sp.runs.cap && ((rc = release_together(c, s, sp.runs)) || (rc = sp.runs.grow(c, sp.nruns, s)))) ||
+        (words > sp.runrec.cap && ((rc = release_together(c, s, sp.runrec)) || (rc = sp.runrec.grow(c, words, s)))) ||
+        (sp.n > sp.brow.cap && ((rc = release_together(c, s, sp.brow)) || (rc = sp.brow.grow(c, sp.n, s)))) ||
+        (sp.h_rbase.size() > sp.rbase.cap && ((rc = release_together(c, s, sp.rbase)) || (rc = sp.rbase.grow(c, sp.h_rbase.size(), s)))))
       return rc;
     HIPCHK(c, hipMemcpyAsync(sp.rbase, sp.h_rbase.data(), sizeof(uint32_t) * sp.h_rbase.size(), hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(sp.runs, sp.h_runs.data(), sizeof(SpecRunDev) * sp.nruns, hipMemcpyHostToDevice, s));
@@ -538,13 +514,7 @@ int plan_launch(mi_rtj_plan* p, const void* d_stream, void* d_out, int what = kL
 
 extern "C" {
 
-int mi_rtj_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  int ok = 0;
-  for (int i = 0; i < n; i++) ok += device_is_gfx950(i) ? 1 : 0;
-  return ok;
-}
+int mi_rtj_device_count(void) { return device_count(); }
 
 mi_rtj_ctx* mi_rtj_create(int device) {
   int n = 0;
@@ -560,7 +530,7 @@ mi_rtj_ctx* mi_rtj_create(int device) {
     fail(nullptr, MI_RTJ_ERR_ARG, "device %d out of range (%d devices)", device, n);
     return nullptr;
   }
-  if (!device_is_gfx950(device)) {
+  if (!is_gfx950(device)) {
     hipDeviceProp_t p;
     (void)hipGetDeviceProperties(&p, device);
     fail(nullptr, MI_RTJ_ERR_NO_DEVICE, "device %d is %s; the kernels are built for gfx950 only", device, p.gcnArchName);
@@ -574,7 +544,7 @@ mi_rtj_ctx* mi_rtj_create(int device) {
     return nullptr;
   };
   if ((e = hipSetDevice(device)) != hipSuccess) return bail("hipSetDevice", e);
-  if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
+  if ((e = hipStreamCreateWithFlags(&c->stream.p, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
   std::vector<QTab> lut(kNumQTab);
   build_all_qtabs(lut.data());
   for (int q = 0; q < kNumQTab; q++) {
@@ -598,18 +568,10 @@ void mi_rtj_destroy(mi_rtj_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->single) mi_rtj_plan_destroy(c->single);
-  if (c->e_input) (void)hipEventDestroy(c->e_input);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;  // (its buffers free themselves)
+  delete c;  // (buffers and e_input, then HostCtx's stream)
 }
 
-const char* mi_rtj_last_error(const mi_rtj_ctx* c) {
-  if (c) return c->err.c_str();
-  std::lock_guard<std::mutex> l(g_err_mu);
-  static thread_local std::string copy;
-  copy = g_create_err;
-  return copy.c_str();
-}
+const char* mi_rtj_last_error(const mi_rtj_ctx* c) { return last_error(c); }
 
 int mi_rtj_set_format(mi_rtj_ctx* c, int fmt) {
   if (!c) return MI_RTJ_ERR_ARG;
@@ -645,27 +607,16 @@ void* mi_rtj_dev_alloc(mi_rtj_ctx* c, size_t bytes) {
   return p;
 }
 
-void mi_rtj_dev_free(mi_rtj_ctx* c, void* d) {
-  if (!c || !d) return;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-}
+void mi_rtj_dev_free(mi_rtj_ctx* c, void* d) { dev_free(c, d); }
 
 int mi_rtj_h2d(mi_rtj_ctx* c, void* d, const void* s, size_t n) {
   if (!c || (!d && n) || (!s && n)) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_h2d: NULL argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return MI_RTJ_OK;
+  return copy_sync(c, d, s, n, hipMemcpyHostToDevice);
 }
 
 int mi_rtj_d2h(mi_rtj_ctx* c, void* dst, const void* d, size_t n) {
   if (!c || (!d && n) || (!dst && n)) return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_d2h: NULL argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(dst, d, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return MI_RTJ_OK;
+  return copy_sync(c, dst, d, n, hipMemcpyDeviceToHost);
 }
 
 int mi_rtj_dev_memset(mi_rtj_ctx* c, void* d, int v, size_t n) {
@@ -676,12 +627,7 @@ int mi_rtj_dev_memset(mi_rtj_ctx* c, void* d, int v, size_t n) {
   return MI_RTJ_OK;
 }
 
-int mi_rtj_sync(mi_rtj_ctx* c) {
-  if (!c) return MI_RTJ_ERR_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return MI_RTJ_OK;
-}
+int mi_rtj_sync(mi_rtj_ctx* c) { return c ? stream_sync(c) : MI_RTJ_ERR_ARG; }
 
 mi_rtj_plan* mi_rtj_plan_create(mi_rtj_ctx* c, int n, const uint8_t* headers, const uint64_t* pkt_offset,
                                 const uint32_t* pkt_len, const uint64_t* out_offset) {
@@ -734,7 +680,7 @@ mi_rtj_plan* mi_rtj_plan_create(mi_rtj_ctx* c, int n, const uint8_t* headers, co
     o.dyn = p->sw.overlap_set ? p->sw.overlap == 2 : !o.on && groups >= (uint64_t)kOverlapMaxGroups;  // (2: tests, on small plans)
     if (p->fmt != MI_RTJ_FMT_YUV420) o.on = o.dyn = false;  // both kernels on the instance's stream
     if ((o.on || o.dyn) && (o.blkoff_b.grow(c, p->n_index, c->stream) != MI_RTJ_OK ||
-                            hipStreamCreateWithFlags(&o.own_idx, hipStreamNonBlocking) != hipSuccess)) {
+                            hipStreamCreateWithFlags(&o.own_idx.p, hipStreamNonBlocking) != hipSuccess)) {
       if (o.on) {
         fail(c, MI_RTJ_ERR_NOMEM, "second block index / index stream of the plan");
         return refuse();
@@ -756,9 +702,7 @@ void mi_rtj_plan_destroy(mi_rtj_plan* p) {
   if (!p) return;
   (void)hipSetDevice(p->ctx->device);
   (void)hipStreamSynchronize(p->ctx->stream);
-  for (auto& v : p->ev) drop_events(v);
-  drop_events(p->run_ev);
-  delete p;  // (every group of its state frees itself)
+  delete p;  // (its events and every group of its state free themselves)
 }
 
 int mi_rtj_plan_decode(mi_rtj_plan* p, const void* d_stream, void* d_out) {
@@ -778,8 +722,9 @@ void mi_rtj_plan_info(const mi_rtj_plan* p, int* n, uint64_t* nb, uint64_t* bi, 
 void mi_rtj_plan_profile(mi_rtj_plan* p, int enable) {
   if (!p) return;
   (void)hipStreamSynchronize(p->ctx->stream);
-  for (auto& v : p->ev) drop_events(v);
-  drop_events(p->run_ev);
+  for (auto& v : p->ev) v.clear();
+  p->run_ev.clear();
+  p->timing.clear();
   p->profile = enable != 0;
   p->launches = 0;
 }
@@ -807,10 +752,17 @@ int mi_rtj_plan_step_times(mi_rtj_plan* p, float* ms, int max_steps, int* steps)
   const int n = (int)p->ev[MI_RTJ_K_DECODE].size();
   *steps = n;
   for (int i = 0; i < n && i < max_steps; i++) {
-    // the kernel that owns its begin event is the first of its launch; k_decode's end event closes the launch
+    // the kernel whose begin event is no kernel's end event is the first of its launch; k_decode's end event closes the launch.
+    // (This takes entry i of every kernel's list to be launch i: true of a plan whose launches all run the same stages,
+    // which the plans this call is made for — batches, kLaunchAll — do)
+    auto ends_a_kernel = [&](hipEvent_t e) {
+      for (const auto& v : p->ev)
+        if ((int)v.size() > i && v[i].b == e) return true;
+      return false;
+    };
     hipEvent_t first = nullptr;
     for (int k = 0; k < MI_RTJ_NUM_KERNELS && !first; k++)
-      if ((int)p->ev[k].size() > i && p->ev[k][i].owns_a) first = p->ev[k][i].a;
+      if ((int)p->ev[k].size() > i && !ends_a_kernel(p->ev[k][i].a)) first = p->ev[k][i].a;
     // (a launch with runs ends with phase 2)
     hipEvent_t last = (int)p->run_ev.size() > i && p->run_ev[i].b ? p->run_ev[i].b : p->ev[MI_RTJ_K_DECODE][i].b;
     float x = 0;
@@ -1103,7 +1055,7 @@ int mi_rtj_decode_nocopy(mi_rtj_ctx* c, const uint8_t* pkt, size_t len, const ui
   const FrameDev& f = c->single->h_frames[0];
   const Format& F = kFormats[c->fmt];
   const size_t ysz = (size_t)f.w * f.h, fsz = frame_plane_bytes(f, c->fmt);
-  const int rc = c->h_frame.grow(c, fsz);
+  const int rc = c->h_frame.grow(c, fsz, nullptr);
   if (rc != MI_RTJ_OK) return rc;
   HIPCHK(c, hipMemcpyAsync(c->h_frame, c->d_frame, fsz, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -1,18 +1,12 @@
 // mi_yuv.hip — C ABI (include/mi_yuv.h) of the MI355X unpacker of the uncompressed QuickTime YUV family.  No CPU path:
 // without a gfx950 device every call but the three host-only queries fails with a message.  The kernels and the format
-// table: yuv_unpack_kernels.h.
+// table: yuv_unpack_kernels.h.  Owned memory, errors, the event timer and the bodies of the calls every device library
+// has: host_base.h.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
-#include <deque>
-#include <mutex>
-#include <string>
-#include <vector>
-
 #include "../../include/mi_yuv.h"
-#include "host_owned.h"
+#include "host_base.h"
 #include "yuv_unpack_kernels.h"
 
 using namespace miyuv;
@@ -21,63 +15,19 @@ static_assert(kYuv2 == MI_YUV_YUV2 && k2vuy == MI_YUV_2VUY && kYv12Lower == MI_Y
                   kVyuy == MI_YUV_VYUY && kYvu9 == MI_YUV_YVU9 && kV308 == MI_YUV_V308 && kV408 == MI_YUV_V408 &&
                   kV410 == MI_YUV_V410 && kV210 == MI_YUV_V210 && kYuv4 == MI_YUV_YUV4 && kCodecs == MI_YUV_CODECS,
               "header and kernels agree");
+static_assert(MI_YUV_OK == kOk && MI_YUV_ERR_HIP == kErrHip, "header and host base agree");
 
-namespace {
-inline hipError_t destroy_stream(void* s) { return hipStreamDestroy((hipStream_t)s); }
-inline hipError_t destroy_event(void* e) { return hipEventDestroy((hipEvent_t)e); }
-using Stream = Owned<ihipStream_t, destroy_stream>;
-using Event = Owned<ihipEvent_t, destroy_event>;
-using DevBytes = Owned<uint8_t, hipFree>;
-using PinnedBytes = Owned<uint8_t, hipHostFree>;
-struct EventPair {
-  Event start, stop;
-};
-}  // namespace
-
-// Members are destroyed last to first: every buffer and event before the stream.
-struct __attribute__((visibility("hidden"))) mi_yuv_ctx {
-  int device = 0;
-  Stream stream;
-  std::string err;
-  // the events around the launches since the last mi_yuv_times (the newest kKeep), and pairs nobody uses
-  static constexpr size_t kKeep = 4096;
-  std::vector<EventPair> ev_free;
-  std::deque<EventPair> ev_used;
+// Device, stream and error text are HostCtx's (host_base.h), destroyed after everything here; the timer goes before
+// the pool it hands its pairs to.
+struct __attribute__((visibility("hidden"))) mi_yuv_ctx : HostCtx {
+  EventPool ev_free;
+  Timer time{ev_free};  // the unpack launches (mi_yuv_times)
   // mi_yuv_unpack_frame's staging: one packet and one picture on the device, the picture in pinned memory; they only grow
-  DevBytes d_packet, d_pic;
-  PinnedBytes h_pic;
+  DevBuf<uint8_t> d_packet, d_pic;
+  PinnedBuf<uint8_t> h_pic;
 };
 
 namespace {
-std::mutex g_mu;
-std::string g_err;
-
-int fail(mi_yuv_ctx* c, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (c) c->err = buf;
-  else {
-    std::lock_guard<std::mutex> l(g_mu);
-    g_err = buf;
-  }
-  return code;
-}
-
-#define YUVCHK(c, call)                                                                                             \
-  do {                                                                                                              \
-    hipError_t e_ = (call);                                                                                         \
-    if (e_ != hipSuccess)                                                                                           \
-      return fail((c), MI_YUV_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);  \
-  } while (0)
-
-bool is_gfx950(int dev) {
-  hipDeviceProp_t p;
-  return hipGetDeviceProperties(&p, dev) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0;
-}
-
 // a codec and a size, checked against the format table: the shape, or a message that names the rule
 int checked_shape(mi_yuv_ctx* c, const char* who, int codec, int w, int h, Shape* s) {
   if (codec < 0 || codec >= kCodecs) return fail(c, MI_YUV_ERR_ARG, "%s: unknown codec %d", who, codec);
@@ -118,92 +68,28 @@ constexpr bool launches_agree() {
 }
 static_assert(launches_agree(), "the plane mover has the codecs the format table gives it");
 
-// a start event, recorded on the stream; the pair is created completely or not at all
-int timer_begin(mi_yuv_ctx* c, EventPair* open) {
-  if (!c->ev_free.empty()) {
-    *open = std::move(c->ev_free.back());
-    c->ev_free.pop_back();
-  } else {
-    EventPair e;  // (a failure below destroys what it holds)
-    YUVCHK(c, hipEventCreate(&e.start.p));
-    YUVCHK(c, hipEventCreate(&e.stop.p));
-    *open = std::move(e);
-  }
-  const hipError_t r = hipEventRecord(open->start, c->stream);
-  if (r == hipSuccess) return MI_YUV_OK;
-  c->ev_free.push_back(std::move(*open));
-  return fail(c, MI_YUV_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(r));
-}
-// the stop event; only a pair recorded on both sides is one mi_yuv_times reads
-int timer_end(mi_yuv_ctx* c, EventPair* open) {
-  const hipError_t r = hipEventRecord(open->stop, c->stream);
-  if (r != hipSuccess) {
-    c->ev_free.push_back(std::move(*open));
-    return fail(c, MI_YUV_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(r));
-  }
-  c->ev_used.push_back(std::move(*open));
-  if (c->ev_used.size() > mi_yuv_ctx::kKeep) {
-    c->ev_free.push_back(std::move(c->ev_used.front()));
-    c->ev_used.pop_front();
-  }
-  return MI_YUV_OK;
-}
-
-// the checked launch over n resident packets, timed
+// the checked launch over n resident packets, timed (a launch that fails leaves the timer's pair open: it goes back to
+// the pool at the next begin())
 int run(mi_yuv_ctx* c, int codec, const Shape& s, const void* d_packets, size_t packet_stride, int n, void* d_pics, size_t pic_stride) {
-  EventPair open;
-  int rc = timer_begin(c, &open);
+  const int rc = c->time.begin(c, c->stream);
   if (rc != MI_YUV_OK) return rc;
   kLaunch[codec](c->stream, s, (const uint8_t*)d_packets, (uint64_t)packet_stride, n, (uint8_t*)d_pics, (uint64_t)pic_stride);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    c->ev_free.push_back(std::move(open));
-    return fail(c, MI_YUV_ERR_HIP, "the launch of %s failed: %s", kFormats[codec].name, hipGetErrorString(e));
-  }
-  return timer_end(c, &open);
+  if (e != hipSuccess) return fail(c, MI_YUV_ERR_HIP, "the launch of %s failed: %s", kFormats[codec].name, hipGetErrorString(e));
+  return c->time.end(c, c->stream);
 }
 
-// room for `bytes` in a staging buffer (the stream is idle between mi_yuv_unpack_frame calls: nothing is waited for)
-template <class B, class A>
-int grow(mi_yuv_ctx* c, B& b, uint64_t bytes, A alloc) {
-  if (bytes <= b.cap) return MI_YUV_OK;
-  b.release();
-  YUVCHK(c, alloc((void**)&b.p, (size_t)bytes));
-  b.cap = bytes;
-  return MI_YUV_OK;
-}
-hipError_t device_malloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
-hipError_t pinned_malloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
 uint64_t up16(uint64_t x) { return (x + 15u) & ~(uint64_t)15u; }
 }  // namespace
 
 extern "C" {
 
-int mi_yuv_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  int ok = 0;
-  for (int i = 0; i < n; i++) ok += is_gfx950(i);
-  return ok;
-}
+int mi_yuv_device_count(void) { return device_count(); }
 
-const char* mi_yuv_last_error(const mi_yuv_ctx* c) {
-  if (c) return c->err.c_str();
-  std::lock_guard<std::mutex> l(g_mu);
-  return g_err.c_str();
-}
+const char* mi_yuv_last_error(const mi_yuv_ctx* c) { return last_error(c); }
 
 mi_yuv_ctx* mi_yuv_create(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-    fail(nullptr, MI_YUV_ERR_HIP, "no HIP device: the YUV unpacker has no CPU path");
-    return nullptr;
-  }
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= n || !is_gfx950(device)) {
-    fail(nullptr, MI_YUV_ERR_ARG, "device %d is not a gfx950 (MI355X) device", device);
-    return nullptr;
-  }
+  if ((device = usable_device(device, "YUV unpacker", MI_YUV_ERR_ARG)) < 0) return nullptr;
   mi_yuv_ctx* c = new mi_yuv_ctx();
   c->device = device;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream.p, hipStreamNonBlocking) != hipSuccess) {
@@ -230,32 +116,16 @@ void* mi_yuv_dev_alloc(mi_yuv_ctx* c, size_t bytes) {
   }
   return d;
 }
-void mi_yuv_dev_free(mi_yuv_ctx* c, void* d) {
-  if (!c || !d) return;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-}
+void mi_yuv_dev_free(mi_yuv_ctx* c, void* d) { dev_free(c, d); }
 int mi_yuv_h2d(mi_yuv_ctx* c, void* d, const void* h, size_t n) {
   if (!c || (!d && n) || (!h && n)) return fail(c, MI_YUV_ERR_ARG, "mi_yuv_h2d: NULL argument");
-  YUVCHK(c, hipSetDevice(c->device));
-  YUVCHK(c, hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, c->stream));
-  YUVCHK(c, hipStreamSynchronize(c->stream));
-  return MI_YUV_OK;
+  return copy_sync(c, d, h, n, hipMemcpyHostToDevice);
 }
 int mi_yuv_d2h(mi_yuv_ctx* c, void* h, const void* d, size_t n) {
   if (!c || (!d && n) || (!h && n)) return fail(c, MI_YUV_ERR_ARG, "mi_yuv_d2h: NULL argument");
-  YUVCHK(c, hipSetDevice(c->device));
-  YUVCHK(c, hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, c->stream));
-  YUVCHK(c, hipStreamSynchronize(c->stream));
-  return MI_YUV_OK;
+  return copy_sync(c, h, d, n, hipMemcpyDeviceToHost);
 }
-int mi_yuv_sync(mi_yuv_ctx* c) {
-  if (!c) return MI_YUV_ERR_ARG;
-  YUVCHK(c, hipSetDevice(c->device));
-  YUVCHK(c, hipStreamSynchronize(c->stream));
-  return MI_YUV_OK;
-}
+int mi_yuv_sync(mi_yuv_ctx* c) { return c ? stream_sync(c) : MI_YUV_ERR_ARG; }
 
 int mi_yuv_codec_of(uint32_t fourcc) {  // the first decoder registered for a fourcc wins: '2vuy' is the UYVY one's
   for (int i = 0; i < kCodecs; i++)
@@ -302,7 +172,7 @@ int mi_yuv_unpack_batch(mi_yuv_ctx* c, int codec, int w, int h, const void* d_pa
   const uintptr_t p0 = (uintptr_t)d_packets, p1 = p0 + (size_t)(n - 1) * packet_stride + (size_t)s.packet_bytes;
   const uintptr_t q0 = (uintptr_t)d_pics, q1 = q0 + (size_t)(n - 1) * pic_stride + (size_t)s.picture_bytes;
   if (p0 < q1 && q0 < p1) return fail(c, MI_YUV_ERR_ARG, "%s: d_packets overlaps d_pics", who);
-  YUVCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->device));
   return run(c, codec, s, d_packets, packet_stride, n, d_pics, pic_stride);
 }
 
@@ -324,16 +194,17 @@ int mi_yuv_unpack_frame(mi_yuv_ctx* c, int codec, int w, int h, const uint8_t* p
   if (len < s.packet_bytes)
     return fail(c, MI_YUV_ERR_FORMAT, "%s: a packet of %zu bytes; %s at %d x %d has %llu", who, len, kFormats[codec].name, w, h,
                 (unsigned long long)s.packet_bytes);
-  YUVCHK(c, hipSetDevice(c->device));
-  rc = grow(c, c->d_packet, up16(s.packet_bytes), device_malloc);
-  if (rc == MI_YUV_OK) rc = grow(c, c->d_pic, up16(s.picture_bytes), device_malloc);
-  if (rc == MI_YUV_OK) rc = grow(c, c->h_pic, s.picture_bytes, pinned_malloc);
+  HIPCHK(c, hipSetDevice(c->device));
+  // (the stream is idle between these calls: nothing is waited for)
+  rc = c->d_packet.grow(c, up16(s.packet_bytes), nullptr);
+  if (rc == MI_YUV_OK) rc = c->d_pic.grow(c, up16(s.picture_bytes), nullptr);
+  if (rc == MI_YUV_OK) rc = c->h_pic.grow(c, s.picture_bytes, nullptr);
   if (rc != MI_YUV_OK) return rc;
-  YUVCHK(c, hipMemcpyAsync(c->d_packet, packet, (size_t)s.packet_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_packet, packet, (size_t)s.packet_bytes, hipMemcpyHostToDevice, c->stream));
   rc = run(c, codec, s, c->d_packet, (size_t)up16(s.packet_bytes), 1, c->d_pic, (size_t)up16(s.picture_bytes));
   if (rc != MI_YUV_OK) return rc;
-  YUVCHK(c, hipMemcpyAsync(c->h_pic, c->d_pic, (size_t)s.picture_bytes, hipMemcpyDeviceToHost, c->stream));
-  YUVCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pic, c->d_pic, (size_t)s.picture_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* tight = c->h_pic;
   for (uint32_t p = 0; p < s.planes; p++) {
     const size_t row = (size_t)s.w[p] * s.bps[p];
@@ -343,24 +214,7 @@ int mi_yuv_unpack_frame(mi_yuv_ctx* c, int codec, int w, int h, const uint8_t* p
 }
 
 int mi_yuv_times(mi_yuv_ctx* c, float* total_ms, int* launches) {
-  if (!c || !total_ms || !launches) return MI_YUV_ERR_ARG;
-  YUVCHK(c, hipSetDevice(c->device));
-  YUVCHK(c, hipStreamSynchronize(c->stream));
-  hipError_t bad = hipSuccess;
-  float sum = 0.f;
-  const int n = (int)c->ev_used.size();
-  for (EventPair& e : c->ev_used) {  // the pairs go back to the pool whether or not every one could be read
-    float ms = 0.f;
-    const hipError_t r = hipEventElapsedTime(&ms, e.start, e.stop);
-    if (r != hipSuccess) bad = r;
-    sum += ms;
-    c->ev_free.push_back(std::move(e));
-  }
-  c->ev_used.clear();
-  if (bad != hipSuccess) return fail(c, MI_YUV_ERR_HIP, "hipEventElapsedTime failed: %s", hipGetErrorString(bad));
-  *total_ms = sum;
-  *launches = n;
-  return MI_YUV_OK;
+  return times(c, c ? &c->time : nullptr, 1, total_ms, launches, MI_YUV_ERR_ARG);
 }
 
 }  // extern "C"

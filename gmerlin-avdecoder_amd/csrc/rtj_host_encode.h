@@ -184,21 +184,19 @@ int mi_rtj_copy_ceiling(mi_rtj_ctx* c, const void* d_src, void* d_dst, size_t by
   if (!c || !d_src || !d_dst || !gbs || bytes < 16 || (bytes & 15) || reps < 1 || ((uintptr_t)d_src & 15) || ((uintptr_t)d_dst & 15))
     return fail(c, MI_RTJ_ERR_ARG, "mi_rtj_copy_ceiling: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
-  hipEvent_t e0, e1;
-  HIPCHK(c, hipEventCreate(&e0));
-  HIPCHK(c, hipEventCreate(&e1));
+  EventPair e;  // (every return destroys what it holds)
+  HIPCHK(c, hipEventCreate(&e.start.p));
+  HIPCHK(c, hipEventCreate(&e.stop.p));
   const size_t n16 = bytes / 16;
   const unsigned grid = (unsigned)std::min<size_t>((n16 + 255) / 256, 256u * 32u);
   hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(256), 0, c->stream, (const uint4*)d_src, (uint4*)d_dst, n16);  // warm-up
-  HIPCHK(c, hipEventRecord(e0, c->stream));
+  HIPCHK(c, hipEventRecord(e.start, c->stream));
   for (int r = 0; r < reps; r++)
     hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(256), 0, c->stream, (const uint4*)d_src, (uint4*)d_dst, n16);
-  HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, hipEventSynchronize(e1));
+  HIPCHK(c, hipEventRecord(e.stop, c->stream));
+  HIPCHK(c, hipEventSynchronize(e.stop));
   float ms = 0;
-  HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  HIPCHK(c, hipEventElapsedTime(&ms, e.start, e.stop));
   *gbs = 2.0 * (double)bytes * reps / ((double)ms * 1e6);
   return MI_RTJ_OK;
 }

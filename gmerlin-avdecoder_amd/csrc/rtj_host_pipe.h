@@ -8,17 +8,17 @@
 // i-1 run side by side on three streams.
 struct PipeSlot {
   mi_rtj_plan* plan = nullptr;
-  PinnedBuf<uint8_t> h_stage;  // FrameDev (64 bytes), then the packet
+  FlagPinnedBuf<uint8_t> h_stage;  // FrameDev (64 bytes), then the packet
   DevBuf<uint8_t> d_stage;     // (its capacity is the staging's)
   DevBuf<uint8_t> own_d_pic;   // the slot's own pictures (sessions without copy groups) ...
-  PinnedBuf<uint8_t> own_h_pic;
+  FlagPinnedBuf<uint8_t> own_h_pic;
   uint8_t* d_pic = nullptr;    // ... and the ones in use: this packet's picture on the device (starts as a copy of its
   uint8_t* h_pic = nullptr;    // predecessor's) and the pinned host picture handed to the caller
   size_t pic_cap = 0;
   bool owns_pic = true;        // false: d_pic / h_pic point into the session's group buffers (copies out in groups)
   int out_state = 0;           // 0 nothing to copy, 1 decoded and waiting for its group's copy out, 2 copy out queued
-  hipEvent_t out_ev = nullptr; // the event that says this picture is in host memory (e_out of the slot that closed the copy)
-  hipEvent_t e_in = nullptr, e_dec = nullptr, e_out = nullptr;
+  hipEvent_t out_ev = nullptr; // the event that says this picture is in host memory (e_out of the slot that closed the copy; borrowed)
+  Event e_in, e_dec, e_out;    // (the slots go before the session's streams: mi_rtj_pipe)
   uint64_t tag = 0;
   int w = 0, h = 0;
   FrameDev fd;                      // (index groups) the packet's descriptor, bases filled in when its group is queued
@@ -29,12 +29,25 @@ struct PipeSlot {
   int issued = 0;                   // 1 once the worker has queued everything up to the copy out (guarded by mu)
   int rc = 0;                       // what queuing it returned
   std::string err;
+
+  PipeSlot() = default;
+  // out of line and hidden: the loop that moves the slots (slot.resize(), once a session) then stays inside the vector's
+  // own function, and the library exports the symbols it did while the events were raw handles
+  __attribute__((noinline, visibility("hidden"))) PipeSlot(PipeSlot&&) noexcept;
 };
+inline PipeSlot::PipeSlot(PipeSlot&&) noexcept = default;
 
 struct mi_rtj_pipe {
   mi_rtj_ctx* ctx = nullptr;
   int depth = 0;
   int max_w = 0, max_h = 0;   // the stream's coded size: packets that announce more are refused
+  // Members are destroyed last to first: the streams are declared in front of the slots and the buffers, whose events
+  // were recorded on them.
+  // kernels run on the instance's stream; packets come in on s_in; pictures leave on s_out[slot & 1]: with one stream a
+  // session has one picture-sized copy out in flight at a time, and the link gives such a copy (3.1 MB at 1080p) 38 GB/s
+  // where two side by side, or larger ones, get past 50 (profiles/r02/pcie_probe.json); MI_RTJ_OUT_STREAMS=1 is the A/B
+  Stream s_in, s_out[2];
+  Stream s_idx;               // MI_RTJ_IDX_STREAM=1 (A/B, slower): index kernels of the packets on a stream of their own
   std::vector<PipeSlot> slot;
   int head = 0, count = 0;    // oldest packet in flight, packets in flight
   int lent = -1;              // slot whose host picture the caller is looking at (until the next mi_rtj_pipe_next)
@@ -43,10 +56,6 @@ struct mi_rtj_pipe {
   // The session's environment switches (rtj_host_switches.h).  stats: where the submitting thread's time goes is printed
   // to stderr when the session ends; threaded: HIP calls on the worker thread (A/B; off by default)
   PipeSwitches sw;
-  // kernels run on the instance's stream; packets come in on s_in; pictures leave on s_out[slot & 1]: with one stream a
-  // session has one picture-sized copy out in flight at a time, and the link gives such a copy (3.1 MB at 1080p) 38 GB/s
-  // where two side by side, or larger ones, get past 50 (profiles/r02/pcie_probe.json); MI_RTJ_OUT_STREAMS=1 is the A/B
-  hipStream_t s_in = nullptr, s_out[2] = {nullptr, nullptr};
   // Pictures leave in groups: the slots of a group lie side by side on the device and in pinned host memory, and one
   // copy takes all of them once the group's last packet is decoded (or as many as are decoded when the caller asks for
   // one earlier).  The link moves a 1080p picture (3.1 MB) at 38 GB/s and 6-12 MB at 47-55 (profiles/r02/pcie_probe.json),
@@ -55,7 +64,7 @@ struct mi_rtj_pipe {
   int group = 1;
   size_t grp_fsz = 0;                    // bytes of one picture in a group buffer
   std::vector<DevBuf<uint8_t>> d_grp;    // [depth / group]
-  std::vector<PinnedBuf<uint8_t>> h_grp;
+  std::vector<FlagPinnedBuf<uint8_t>> h_grp;
   // The INDEX of the packets is built in groups as well (MI_RTJ_IDX_GROUP = 1 / 2 / 4, default: the copy group): the
   // exact index of ONE 1080p packet is three launches that each run one round of workgroups or one serial chain
   // (k_index_summarize 19 us, k_index_resolve 21, k_index_emit 13, tools/one_packet_kernels.py) and take as long for
@@ -66,9 +75,8 @@ struct mi_rtj_pipe {
   int igroup = 1;
   int nstaged = 0;                     // slots staged and not yet queued: the last `nstaged` submitted
   std::vector<mi_rtj_plan*> gplan;     // [depth / igroup]
-  PinnedBuf<FrameDev> h_desc;          // [depth]
+  FlagPinnedBuf<FrameDev> h_desc;      // [depth]
   DevBuf<FrameDev> d_desc;             // [depth]
-  hipStream_t s_idx = nullptr;         // MI_RTJ_IDX_STREAM=1 (A/B, slower): index kernels of the packets on a stream of their own
   uint64_t submitted = 0, returned = 0;
   // MI_RTJ_PIPE_STATS=1 (seconds): [0] copying packets into pinned staging, [1] runtime calls that queue work, [2] waiting
   // for a picture's copy out; t_d2h_call: inside hipMemcpyAsync of the copy out (part of t_issue)
@@ -321,18 +329,18 @@ mi_rtj_pipe* mi_rtj_pipe_create(mi_rtj_ctx* c, int depth, int max_w, int max_h) 
     return (prio_lo != prio_hi ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio)
                                : hipStreamCreateWithFlags(st, hipStreamNonBlocking)) == hipSuccess;
   };
-  bool ok = make_stream(&q->s_in, prio_hi);
+  bool ok = make_stream(&q->s_in.p, prio_hi);
   // off unless asked for: with the index on a stream of its own a 1080p session ran at 6,600 pictures per second
   // instead of 12,000 (profiles/r03/e2e_ab.txt) — every packet then crosses streams twice more, and the runtime's
   // cross-stream waits cost more than the overlap of one packet's index with its predecessor's transform gives
-  if (q->sw.idx_stream) ok = ok && hipStreamCreateWithFlags(&q->s_idx, hipStreamNonBlocking) == hipSuccess;
-  for (int i = 0; i < q->sw.out_streams; i++) ok = ok && make_stream(&q->s_out[i], prio_lo);
+  if (q->sw.idx_stream) ok = ok && hipStreamCreateWithFlags(&q->s_idx.p, hipStreamNonBlocking) == hipSuccess;
+  for (int i = 0; i < q->sw.out_streams; i++) ok = ok && make_stream(&q->s_out[i].p, prio_lo);
   for (auto& sl : q->slot) {
     sl.plan = plan_new(c, 1, kPlanSessionSlot);
     sl.plan->idx_stream = q->s_idx;
-    ok = ok && hipEventCreateWithFlags(&sl.e_in, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&sl.e_dec, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&sl.e_out, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&sl.e_in.p, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&sl.e_dec.p, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&sl.e_out.p, hipEventDisableTiming) == hipSuccess;
   }
   if (ok && q->igroup > 1) {  // one plan per index group, the descriptors of all slots in one array
     ok = q->h_desc.alloc((uint64_t)depth) == hipSuccess && q->d_desc.grow(c, (uint64_t)depth, c->stream) == MI_RTJ_OK;
@@ -389,21 +397,10 @@ void mi_rtj_pipe_destroy(mi_rtj_pipe* q) {
   (void)hipStreamSynchronize(c->stream);
   for (hipStream_t so : q->s_out)
     if (so) (void)hipStreamSynchronize(so);
-  for (auto& sl : q->slot) {
-    mi_rtj_plan_destroy(sl.plan);  // (a plan frees what it owns: its descriptors are the slot's staging)
-    if (sl.e_in) (void)hipEventDestroy(sl.e_in);
-    if (sl.e_dec) (void)hipEventDestroy(sl.e_dec);
-    if (sl.e_out) (void)hipEventDestroy(sl.e_out);
-  }
+  for (auto& sl : q->slot) mi_rtj_plan_destroy(sl.plan);  // (a plan frees what it owns: its descriptors are the slot's staging)
   for (mi_rtj_plan* gp : q->gplan) mi_rtj_plan_destroy(gp);
-  if (q->s_in) (void)hipStreamDestroy(q->s_in);
-  if (q->s_idx) {
-    (void)hipStreamSynchronize(q->s_idx);
-    (void)hipStreamDestroy(q->s_idx);
-  }
-  for (hipStream_t so : q->s_out)
-    if (so) (void)hipStreamDestroy(so);
-  delete q;  // (staging, pictures, group buffers and descriptors free themselves)
+  if (q->s_idx) (void)hipStreamSynchronize(q->s_idx);
+  delete q;  // (the slots' events, staging, pictures, group buffers and descriptors, then the streams)
 }
 
 int mi_rtj_pipe_room(const mi_rtj_pipe* q) {

@@ -5,12 +5,19 @@
 
 namespace {
 
-void drop_events(std::vector<Timed>& v) {
-  for (auto& t : v) {
-    if (t.a && t.owns_a) (void)hipEventDestroy(t.a);
-    if (t.b) (void)hipEventDestroy(t.b);
-  }
-  v.clear();
+#define STAGE_CHK(call)                              \
+  do {                                               \
+    const int rc_ = (call);                          \
+    if (rc_ != MI_RTJ_OK) return rc_;                \
+  } while (0)
+
+// a timing event of the plan's: it lives until profiling is switched or the plan goes
+int timing_event(mi_rtj_plan* p, hipEvent_t* e) {
+  Event ev;
+  HIPCHK(p->ctx, hipEventCreate(&ev.p));
+  *e = ev;
+  p->timing.push_back(std::move(ev));
+  return MI_RTJ_OK;
 }
 
 // While profiling: one event after every kernel; a kernel's start is its predecessor's end (they run back to back on one
@@ -26,27 +33,21 @@ struct KernelClock {
     t = Timed();
     if (prev) {
       t.a = prev;
-      t.owns_a = false;
       return MI_RTJ_OK;
     }
-    HIPCHK(p->ctx, hipEventCreate(&t.a));
+    STAGE_CHK(timing_event(p, &t.a));
     HIPCHK(p->ctx, hipEventRecord(t.a, cur));
     return MI_RTJ_OK;
   }
   int end(int k) {
     if (!p->profile) return MI_RTJ_OK;
-    HIPCHK(p->ctx, hipEventCreate(&t.b));
+    STAGE_CHK(timing_event(p, &t.b));
     HIPCHK(p->ctx, hipEventRecord(t.b, cur));
     p->ev[k].push_back(t);
     prev = t.b;
     return MI_RTJ_OK;
   }
 };
-#define STAGE_CHK(call)                              \
-  do {                                               \
-    const int rc_ = (call);                          \
-    if (rc_ != MI_RTJ_OK) return rc_;                \
-  } while (0)
 
 // what the stages of one launch share
 struct Launch {
@@ -162,7 +163,7 @@ int launch_open(Launch& L, int what) {
   // (a launch that overlaps behind one that did not: whatever the instance's stream still has queued — the last launch's
   // transform reading the first index, the plan's descriptors on their way — comes first)
   if (L.is != L.ds && (c->input_dirty || (L.ov && !p->ov.on && !p->ov.last_overlapped))) {  // something queued on the instance's stream may still be writing the packets
-    if (!c->e_input) HIPCHK(c, hipEventCreateWithFlags(&c->e_input, hipEventDisableTiming));
+    if (!c->e_input) HIPCHK(c, hipEventCreateWithFlags(&c->e_input.p, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->e_input, L.ds));
     HIPCHK(c, hipStreamWaitEvent(L.is, c->e_input, 0));
   }
@@ -171,7 +172,7 @@ int launch_open(Launch& L, int what) {
   if (L.ov) {
     // the launch before last read this index: its k_decode must be through with it
     if (p->ov.e_read[p->ov.flip]) HIPCHK(c, hipStreamWaitEvent(L.is, p->ov.e_read[p->ov.flip], 0));
-    else HIPCHK(c, hipEventCreateWithFlags(&p->ov.e_read[p->ov.flip], hipEventDisableTiming));
+    else HIPCHK(c, hipEventCreateWithFlags(&p->ov.e_read[p->ov.flip].p, hipEventDisableTiming));
   }
   return MI_RTJ_OK;
 }
@@ -266,7 +267,7 @@ int stage_exact_index(Launch& L, const ExactGrids& g) {
 int launch_hand_over(Launch& L, int what) {
   mi_rtj_plan* p = L.p;
   if (L.is != L.ds) {  // k_decode waits for the index (and, through it, for the packet's copy in)
-    if (!p->ov.e_idx) HIPCHK(L.c, hipEventCreateWithFlags(&p->ov.e_idx, hipEventDisableTiming));
+    if (!p->ov.e_idx) HIPCHK(L.c, hipEventCreateWithFlags(&p->ov.e_idx.p, hipEventDisableTiming));
     HIPCHK(L.c, hipEventRecord(p->ov.e_idx, L.is));
     HIPCHK(L.c, hipStreamWaitEvent(L.ds, p->ov.e_idx, 0));
     L.clk.prev = nullptr;  // (profiling) k_decode's start is not the end of a kernel on another stream
@@ -371,8 +372,7 @@ int stage_runs(Launch& L, bool runs, const RunGrids& g, uint8_t* out) {
   if (p->profile) {
     Timed rt;
     rt.a = L.clk.prev;
-    rt.owns_a = false;
-    if (runs) HIPCHK(L.c, hipEventCreate(&rt.b));
+    if (runs) STAGE_CHK(timing_event(p, &rt.b));
     p->run_ev.push_back(rt);
   }
   if (!runs) return MI_RTJ_OK;

@@ -1,4 +1,4 @@
-"""The host layer's buffers when they have to grow (csrc/rtj_host_buf.h, DevBuf::grow): an instance, a plan and a session
+"""The host layer's buffers when they have to grow (csrc/host_base.h, GrowBuf::grow): an instance, a plan and a session
 are fed pictures that outgrow what they hold, then smaller ones that reuse it, then larger ones again — every picture
 bit for bit against the oracle (4:2:2 and greyscale: the restatement of tests/rtjfmt.py), on the smallest pictures that
 force a reallocation.  Every object is closed explicitly: a double free or a freed view would end the process there.
@@ -168,4 +168,26 @@ def test_session_flushed_inside_an_index_group_and_refilled(monkeypatch):
                 got += 1
     assert got == len(pkts)
     pipe.close()
+    dev.close()
+
+
+# ---- mi_rtj_copy_ceiling: its two events are the call's own (csrc/host_base.h, EventPair); a refused call writes nothing ----
+def test_copy_ceiling_copies_and_refuses_without_writing():
+    dev = P.MiRtj()
+    n = 4096
+    src = (np.arange(n, dtype=np.uint32) * 2654435761 >> 13).astype(np.uint8)
+    d_src, d_dst = dev.alloc(n + 16), dev.alloc(n + 16)
+    dev.h2d(d_src, src)
+    dev.memset(d_dst, 0xA5, n + 16)
+    assert dev.copy_ceiling(d_src, d_dst, n, reps=2) > 0
+    assert first_diff(dev.d2h(d_dst, n), src) is None
+    assert (dev.d2h(d_dst, 16, offset=n) == 0xA5).all()  # nothing behind the bytes asked for
+    dev.memset(d_dst, 0x5A, n + 16)
+    for bad in (dict(nbytes=24), dict(nbytes=n, d_src=d_src + 4), dict(nbytes=n, d_dst=d_dst + 8), dict(nbytes=n, reps=0)):
+        args = dict(dict(d_src=d_src, d_dst=d_dst, reps=2), **bad)
+        with pytest.raises(P.MiRtjError, match=r"rc=-3: mi_rtj_copy_ceiling: bad argument"):
+            dev.copy_ceiling(args["d_src"], args["d_dst"], args["nbytes"], reps=args["reps"])
+        assert (dev.d2h(d_dst, n + 16) == 0x5A).all(), bad
+    dev.free(d_src)
+    dev.free(d_dst)
     dev.close()
