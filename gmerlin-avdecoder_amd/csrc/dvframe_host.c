@@ -1,6 +1,6 @@
 /*
  * dvframe_host.c — DV DIF-frame handling on the host; see include/mi_dvframe.h.
- * Byte shuffling only: stays C on the CPU by design.  PARITY UNPINNED (header).
+ * Byte shuffling only: stays C on the CPU by design.  The readers are pinned to lib/dvframe.c where it is defined (header).
  */
 #include "mi_dvframe.h"
 
@@ -23,8 +23,8 @@ static const uint16_t shuffle625[12][9] = {
     {13, 49, 85, 3, 39, 75, 29, 65, 101},  {19, 55, 91, 9, 45, 81, 35, 71, 107},
     {25, 61, 97, 15, 51, 87, 5, 41, 77},   {31, 67, 103, 21, 57, 93, 11, 47, 83}};
 
-#define NTSC_AUDIO 90, {1580, 1452, 1053}, shuffle525
-#define PAL_AUDIO 108, {1896, 1742, 1264}, shuffle625
+#define NTSC_AUDIO 90, {1580, 1452, 1053}, shuffle525, 10
+#define PAL_AUDIO 108, {1896, 1742, 1264}, shuffle625, 12
 #define SAR_NTSC {{10, 11}, {40, 33}}
 #define SAR_PAL {{59, 54}, {118, 81}}
 #define SAR_SQ {{1, 1}, {1, 1}}
@@ -39,7 +39,7 @@ static const mi_dv_profile profiles[] = {
     {0, 0x14, 480000, 10, 4, 30000, 1001, 30, 1280, 1080, SAR_SQ, MI_DV_PIX_422, 8, NTSC_AUDIO},   /* 1080i60 */
     {1, 0x14, 576000, 12, 4, 25, 1, 25, 1440, 1080, SAR_SQ, MI_DV_PIX_422, 8, PAL_AUDIO},          /* 1080i50 */
     {0, 0x18, 240000, 10, 2, 60000, 1001, 60, 960, 720, SAR_SQ, MI_DV_PIX_422, 8, NTSC_AUDIO},     /* 720p60 */
-    {1, 0x18, 288000, 12, 2, 50, 1, 50, 960, 720, SAR_SQ, MI_DV_PIX_422, 8, NTSC_AUDIO},           /* 720p50: 525 audio layout in the reference */
+    {1, 0x18, 288000, 12, 2, 50, 1, 50, 960, 720, SAR_SQ, MI_DV_PIX_422, 8, NTSC_AUDIO},           /* 720p50: 525 audio layout in the reference: 12 sequences, 10 rows */
 };
 
 int mi_dv_num_profiles(void) { return (int)(sizeof profiles / sizeof profiles[0]); }
@@ -153,6 +153,7 @@ int mi_dv_extract_audio(const mi_dv_profile *p, const uint8_t *frame, uint8_t *p
         const uint8_t *blk =
             frame + ((size_t)(c * p->difseg_size + q) * DIF_SEQ_BLOCKS + AUDIO_FIRST + AUDIO_EVERY * j) * DIF_BLOCK + AUDIO_PAYLOAD;
         if (!twelve) {
+          if (q >= p->audio_shuffle_rows) continue; /* 720p50: no row for sequences 10, 11 (the reference reads past its table) */
           const int base = p->audio_shuffle[q][j];
           for (int n = 0; n < 36; n++) {
             const int slot = base + n * p->audio_stride;
@@ -162,14 +163,15 @@ int mi_dv_extract_audio(const mi_dv_profile *p, const uint8_t *frame, uint8_t *p
             put_le16(pcm, slot, v);
           }
         } else {
-          const int base_l = p->audio_shuffle[q % half][j], base_r = p->audio_shuffle[q % half + half][j];
+          const int row_l = q % half, row_r = q % half + half; /* row_l < half <= rows; row_r may have no row (720p50) */
+          const int base_l = p->audio_shuffle[row_l][j], base_r = row_r < p->audio_shuffle_rows ? p->audio_shuffle[row_r][j] : -1;
           for (int n = 0; n < 24; n++) {
             const uint8_t *t = blk + 3 * n;
             const unsigned l = (unsigned)t[0] << 4 | t[2] >> 4, r = (unsigned)t[1] << 4 | (t[2] & 0x0fu);
             const int slot_l = base_l + n * p->audio_stride, slot_r = base_r + n * p->audio_stride;
             if (slot_l >= slots) continue; /* the reference tests the left slot only; the right one lies beside it */
             put_le16(pcm, slot_l, l == 0x800u ? 0u : mi_dv_audio_12to16((uint16_t)l));
-            put_le16(pcm, slot_r, r == 0x800u ? 0u : mi_dv_audio_12to16((uint16_t)r));
+            if (base_r >= 0) put_le16(pcm, slot_r, r == 0x800u ? 0u : mi_dv_audio_12to16((uint16_t)r));
           }
         }
       }

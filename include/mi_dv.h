@@ -208,8 +208,10 @@ int mi_dv_encode_stats(mi_dv_ctx *c, long long qno_hist[16], long long *dropped)
  * What include/mi_dvframe.h's host reader does with one frame, for a batch: the AAUX source pack of every frame (audio
  * block 3 of sequence 0: samples beyond the rate's minimum, rate, quantisation), then the de-shuffle of its audio blocks
  * into interleaved stereo PCM, byte for byte what that reader writes into zeroed buffers (the statement: tests/dvaudio.py).
- * PARITY UNPINNED like the reader.  The other way round only 16-bit sound is written; the AAUX packs it writes are this
- * repository's reading of IEC 61834-4 (nothing in the reference writes any): this library's readers read them back. */
+ * Reading is pinned like the reader, to lib/dvframe.c where that is defined (include/mi_dvframe.h; the kernel is held to
+ * the reference's recorded answers by tests/test_gpu_dv_reference.py).  The other way round only 16-bit sound is written;
+ * the AAUX packs it writes are this repository's reading of IEC 61834-4 and UNPINNED (nothing in the reference writes
+ * any): this library's readers read them back. */
 enum { MI_DV_AUDIO_PAIRS = 4, MI_DV_AUDIO_PAIR_BYTES = 8192 };
 /* n resident frames of `system` -> d_pcm[n][pairs][MI_DV_AUDIO_PAIR_BYTES] (interleaved stereo S16LE, 16-byte aligned),
  * d_info[n][4] int32 (4-byte aligned): samples per channel (0: no source pack, -1: unsupported quantisation or rate), and,
@@ -243,8 +245,9 @@ size_t mi_dv_audio_copy_tables(void *out, size_t cap);
  *
  * What include/mi_dvframe.h's mi_dv_timecode, mi_dv_date, mi_dv_time and mi_dv_pixel_aspect answer for one host frame,
  * for a batch (the statement: tests/dvmeta.py); and the writer of the two subcode and three VAUX DIF blocks of every
- * sequence, which the encoder leaves blank.  PARITY UNPINNED: the readers restate GetSSYBPack and its users
- * (lib/dvframe.c:678-783, :460-471); the packs written are this repository's reading of IEC 61834-2/-4 from memory
+ * sequence, which the encoder leaves blank.  The readers restate GetSSYBPack and its users (lib/dvframe.c:678-783,
+ * :460-471) and are pinned to that file (include/mi_dvframe.h; tests/test_gpu_dv_reference.py for the kernel).  PARITY
+ * UNPINNED in the writing direction: the packs written are this repository's reading of IEC 61834-2/-4 from memory
  * (nothing in the reference writes any), and what is checked is that this library's readers, on host and device, read
  * them back. */
 enum {

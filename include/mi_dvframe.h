@@ -10,9 +10,19 @@
  * mi_dv_timecode, mi_dv_date, mi_dv_time and mi_dv_pixel_aspect here answer.  DV *pixel*
  * decoding (row D4) is libavcodec's in the reference and is not part of this repository.
  *
- * PARITY UNPINNED: lib/dvframe.c cannot be compiled in the build container (it needs gavl
- * through avdec_private.h) and the reference has no tests or vectors for it; the tests check this
- * file against an independent numpy restatement of the same lines only.
+ * PARITY: the reading side (profile detection, the audio de-shuffle, timecode, date, time, pixel aspect) is pinned to
+ * lib/dvframe.c where that file is defined: where the reference tree is present, oracle/Makefile builds the file itself
+ * against a stand-in avdec_private.h (oracle/dvframe_ref/), tests/test_dvframe_reference_cpu.py compares this file with it
+ * call for call, and tests/golden/dvframe_ref.json keeps its answers for checkouts without the tree.  The reference has no
+ * defined answer, and is not compared, for: a rate field above 2 (it indexes past audio_min_samples), the 720p50 profile
+ * (below), frames that walk past the fourth pair buffer (12-bit sound on the 1080 profiles and on a 720p first half
+ * frame), a 720p first half frame given fewer than three pair buffers (it writes through the NULL third one), and frames
+ * with no profile.
+ *
+ * DEPARTS FROM THE REFERENCE at 720p50: that profile has 12 DIF sequences a channel but uses the 10-row 525/60 shuffle
+ * table, and lib/dvframe.c:587,603,609 index rows 10 and 11 (and, in 12-bit mode, rows 6 + 4 and 6 + 5) past the table:
+ * undefined behaviour.  Here a profile carries its table's row count (audio_shuffle_rows) and mi_dv_extract_audio drops
+ * every sample whose row index is at or above it; the return value is what it was.
  */
 #ifndef MI_DVFRAME_H
 #define MI_DVFRAME_H
@@ -41,6 +51,7 @@ typedef struct {
   int audio_stride;
   int audio_min_samples[3]; /* 48, 44.1, 32 kHz */
   const uint16_t (*audio_shuffle)[9];
+  int audio_shuffle_rows;   /* rows of audio_shuffle: 10 or 12; below difseg_size for 720p50 (see above) */
 } mi_dv_profile;
 
 /* D1: dv_frame_profile (lib/dvframe.c:298-316).  frame: at least 480 bytes.  NULL if unknown. */
@@ -57,7 +68,8 @@ int mi_dv_video_packet(const mi_dv_profile *p, const uint8_t *frame, uint8_t *ou
 /* D3: dv_extract_audio (lib/dvframe.c:545-628) with dv_audio_12to16 (:521-543).
  * pcm[0..3]: interleaved-stereo S16 buffers per channel pair (NULL when absent), little endian.
  * Returns samples per channel, 0 when the frame has no audio source pack, -1 for an unsupported
- * quantisation. */
+ * quantisation or rate.  A sample whose shuffle row is at or above audio_shuffle_rows is dropped (720p50 only: DIF
+ * sequences 10 and 11 in 16-bit mode, the right samples of sequences 4, 5, 10 and 11 in 12-bit mode). */
 int mi_dv_extract_audio(const mi_dv_profile *p, const uint8_t *frame, uint8_t *pcm[4]);
 uint16_t mi_dv_audio_12to16(uint16_t sample);
 /* audio stream parameters as bgav_dv_dec_init_audio derives them (lib/dvframe.c:424-462);

@@ -3,8 +3,9 @@
  * lib/video_yuv.c (SURVEY.md layer L2), n packets resident in device memory -> n tightly packed pictures in one launch.
  * Plain C types only; libmi_yuv.so.
  *
- * PINNED BY STATEMENT: every line of the arithmetic is in lib/video_yuv.c and is cited below; that file cannot be compiled
- * here (it needs gavl), so the checker is tests/yuvraw.py, a numpy restatement of the cited lines, and the kernels
+ * PINNED BY STATEMENT: every line of the arithmetic is in lib/video_yuv.c and is cited below; the checker is
+ * tests/yuvraw.py, a numpy restatement of the cited lines, which tests/test_yuv_reference_cpu.py holds to the file itself
+ * (built as it stands into oracle/_ref/libvideo_yuv_ref.so where the reference tree is present), and the kernels
  * reproduce it byte for byte.
  *
  * PAD(x, a) rounds x up to a multiple of a (lib/video_yuv.c:32); words are little-endian (GAVL_PTR_2_32LE).  A PICTURE is

@@ -1,0 +1,1 @@
+/* empty on purpose: the reference's lib/video_yuv.c includes <codecs.h> and takes nothing from it (oracle/Makefile) */

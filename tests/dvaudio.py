@@ -2,8 +2,9 @@
 INFRASTRUCTURE ONLY: the product never imports it.  numpy, no ctypes: the layout data are written out here, not read from
 the library; tests/test_dv_audio_cpu.py holds this file to csrc/dvframe_host.c's mi_dv_extract_audio and to
 np_extract_audio of tests/test_dvframe_host.py, and tests/test_gpu_dv_audio.py holds the kernels to this file, byte for byte.
-UNPINNED like both: the de-shuffle restates lib/dvframe.c:545-628, the AAUX packs that write() makes are this repository's
-reading of IEC 61834-4."""
+extract() restates lib/dvframe.c:545-628 and is PINNED to that file where it is defined (tests/test_dvframe_reference_cpu.py,
+tests/test_dvframe_fixtures_cpu.py); the AAUX packs that write() makes are this repository's reading of IEC 61834-4 and
+stay UNPINNED."""
 import numpy as np
 
 PAIRS, PAIR_BYTES, SLOTS = 4, 8192, 4096

@@ -4,8 +4,9 @@ ctypes: tests/test_dv_meta_cpu.py holds this file to csrc/dvframe_host.c's reade
 mi_dv_pixel_aspect) and to Python's datetime, and tests/test_gpu_dv_meta.py holds the kernels to this file, value for value
 and byte for byte.
 
-UNPINNED: extract() restates GetSSYBPack and its users (lib/dvframe.c:678-783, :460-471); the packs write() makes are this
-repository's reading of IEC 61834-2/-4 from memory; what is checked is that the library's own
+extract() restates GetSSYBPack and its users (lib/dvframe.c:678-783, :460-471) and its fields 0-4 and 6-12 are PINNED to
+that file (tests/test_dvframe_reference_cpu.py, tests/test_dvframe_fixtures_cpu.py).  UNPINNED: the packs write() makes are
+this repository's reading of IEC 61834-2/-4 from memory; what is checked is that the library's own
 readers, on host and on device, read them back.  The readers' two-digit year has a pivot (below 25: 20xx, else 19xx), so a
 year from 2025 on that write() records reads back as 19xx: the reference's rule, kept."""
 import numpy as np

@@ -1,7 +1,10 @@
-"""Host-side DV DIF-frame handling (include/mi_dvframe.h).  PARITY UNPINNED:
-the reference's lib/dvframe.c cannot be built here (gavl), so these tests compare the C module with
-an independent numpy restatement of the same lines on synthetic DIF frames built to the layout the
-code assumes, plus a few hand-made anchors."""
+"""Host-side DV DIF-frame handling (include/mi_dvframe.h).  These tests compare the
+C module with an independent numpy restatement of the reference's lines on synthetic DIF frames built to
+the layout the code assumes, plus a few hand-made anchors.  The readers are pinned to lib/dvframe.c itself,
+where that file is defined, by tests/test_dvframe_reference_cpu.py (live, where oracle/_ref has the build) and
+tests/test_dvframe_fixtures_cpu.py (its recorded answers); np_extract_audio below is held to it there too.
+At 720p50 the reference indexes past its 10-row shuffle table: the C module and the restatement both drop
+the samples that have no row (include/mi_dvframe.h)."""
 import ctypes as C
 import os
 import subprocess
@@ -20,7 +23,7 @@ class Profile(C.Structure):
                 ("n_difchan", C.c_int), ("frame_rate", C.c_int), ("frame_rate_base", C.c_int), ("ltc_divisor", C.c_int),
                 ("width", C.c_int), ("height", C.c_int), ("sar", (C.c_int * 2) * 2), ("pix_fmt", C.c_int), ("bpm", C.c_int),
                 ("audio_stride", C.c_int), ("audio_min_samples", C.c_int * 3),
-                ("audio_shuffle", C.POINTER(C.c_uint16 * 9))]
+                ("audio_shuffle", C.POINTER(C.c_uint16 * 9)), ("audio_shuffle_rows", C.c_int)]
 
 
 @pytest.fixture(scope="module")
@@ -72,8 +75,10 @@ def np_12to16(s):
 
 
 def np_extract_audio(p, f, have):
-    """Independent restatement of dv_extract_audio (lib/dvframe.c:545-628)."""
-    shuffle = [[p.audio_shuffle[i][j] for j in range(9)] for i in range(p.difseg_size)]
+    """Independent restatement of dv_extract_audio (lib/dvframe.c:545-628).  Where the reference indexes a shuffle row
+    the table does not have (720p50: 12 sequences, 10 rows), the sample is dropped, as include/mi_dvframe.h says."""
+    rows = p.audio_shuffle_rows
+    shuffle = [[p.audio_shuffle[i][j] for j in range(9)] for i in range(rows)]
     o = 80 * 6 + 80 * 16 * 3 + 3
     smpls, freq, quant = int(f[o + 1]) & 0x3F, (int(f[o + 4]) >> 3) & 7, int(f[o + 4]) & 7
     size = (p.audio_min_samples[freq] + smpls) * 4
@@ -97,7 +102,7 @@ def np_extract_audio(p, f, have):
                 d = 8
                 while d < 80:
                     if quant == 0:
-                        of = shuffle[i][j] + (d - 8) // 2 * p.audio_stride
+                        of = shuffle[i][j] + (d - 8) // 2 * p.audio_stride if i < rows else size
                         if of * 2 < size:
                             pcm[of * 2], pcm[of * 2 + 1] = f[pos + d + 1], f[pos + d]
                             if pcm[of * 2 + 1] == 0x80 and pcm[of * 2] == 0:
@@ -110,8 +115,9 @@ def np_extract_audio(p, f, have):
                         of = shuffle[i % half][j] + (d - 8) // 3 * p.audio_stride
                         if of * 2 < size:
                             pcm[of * 2], pcm[of * 2 + 1] = lc & 0xFF, lc >> 8
-                            of = shuffle[i % half + half][j] + (d - 8) // 3 * p.audio_stride
-                            pcm[of * 2], pcm[of * 2 + 1] = rc & 0xFF, rc >> 8
+                            if i % half + half < rows:
+                                of = shuffle[i % half + half][j] + (d - 8) // 3 * p.audio_stride
+                                pcm[of * 2], pcm[of * 2 + 1] = rc & 0xFF, rc >> 8
                             d += 1
                     d += 2
                 pos += 16 * 80
@@ -161,7 +167,7 @@ def test_12_to_16_expansion(L):
     assert L.mi_dv_audio_12to16(0x7FF) == 0x7FC0 and L.mi_dv_audio_12to16(0x800) == 0x803F  # +full / error code
 
 
-@pytest.mark.parametrize("pi,quant,freq", [(0, 0, 0), (0, 0, 1), (0, 1, 2), (1, 0, 0), (1, 1, 2), (3, 0, 0), (6, 0, 0), (7, 0, 0)])
+@pytest.mark.parametrize("pi,quant,freq", [(0, 0, 0), (0, 0, 1), (0, 1, 2), (1, 0, 0), (1, 1, 2), (3, 0, 0), (6, 0, 0), (7, 0, 0), (8, 0, 0), (8, 1, 2)])
 def test_audio_deshuffle(L, pi, quant, freq):
     rng = np.random.default_rng(10 * pi + quant)
     pp = L.mi_dv_profile_at(pi)

@@ -1,7 +1,7 @@
 """GPU parity of the DV sound — k_dv_audio_extract<Sys> and k_dv_audio_write<Sys> through mi_dv_audio_batch and
 mi_dv_audio_write_batch — against the statement tests/dvaudio.py (which tests/test_dv_audio_cpu.py holds to the host
 reader), byte for byte over every byte of d_pcm, d_info and the frames, in all five systems.  Every case is a few frames.
-UNPINNED: see tests/dvaudio.py."""
+What is pinned to the reference and what is not: see tests/dvaudio.py."""
 import importlib
 
 import numpy as np

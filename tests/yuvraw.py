@@ -1,8 +1,9 @@
 """The uncompressed QuickTime YUV family as upstream decodes it: a numpy restatement of lib/video_yuv.c, the checker of
 libmi_yuv.so (include/mi_yuv.h).
 
-The reference cannot be compiled here: video_yuv.c needs gavl, which is not available, and nothing new is built under
-oracle/.  So the pin is this restatement, written from the upstream lines cited at every function and from nothing in
+tests/test_yuv_reference_cpu.py holds this file to lib/video_yuv.c itself, which oracle/Makefile builds as it stands into
+oracle/_ref/libvideo_yuv_ref.so where the reference tree is present (tests/yuvref.py), and tests/golden/yuv_ref.json keeps
+that build's pictures for checkouts without it.  The restatement is written from the upstream lines cited at every function and from nothing in
 csrc/: each function below is the upstream loop of those lines with numpy slices for its `for`, reading the packet at
 upstream's strides (`priv->frame->strides`, set in the init_* functions) and writing a picture whose planes lie back to
 back, each plane's rows at its own width (`f->strides[p]` = the row), 16-bit samples as native uint16.
