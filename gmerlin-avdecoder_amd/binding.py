@@ -1,40 +1,77 @@
 """ctypes view of include/mi_rtjpeg.h.  No CPU fallback: if the library is missing or there is no
 gfx950 device, construction raises MiRtjError with the library's own message."""
 import ctypes as C
-import os
 import weakref
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
-
-u8p = C.POINTER(C.c_uint8)
-u32p = C.POINTER(C.c_uint32)
-u64p = C.POINTER(C.c_uint64)
+from ._capi import Device, Library, cint, f32p, i64p, intp, sz, u8p, u8pp, u32, u32p, u64, u64p, vp
 
 
 class MiRtjError(RuntimeError):
     pass
 
 
-def lib_path():
-    # MI_RTJ_LIB: an alternative build of the same library (A/B experiments under tools/)
-    return os.environ.get("MI_RTJ_LIB") or os.path.join(HERE, "lib", "libmi_rtjpeg.so")
-
-
-EXPORTS = ["mi_rtj_device_count", "mi_rtj_create", "mi_rtj_destroy", "mi_rtj_last_error", "mi_rtj_decode",
-           "mi_rtj_get_state", "mi_rtj_dev_alloc", "mi_rtj_dev_free", "mi_rtj_h2d", "mi_rtj_d2h",
-           "mi_rtj_dev_memset", "mi_rtj_sync", "mi_rtj_plan_create", "mi_rtj_plan_destroy",
-           "mi_rtj_plan_decode", "mi_rtj_plan_info", "mi_rtj_plan_profile", "mi_rtj_plan_times",
-           "mi_rtj_plan_read_index", "mi_rtj_synth_frames", "mi_rtj_synth_frames_lcg", "mi_rtj_encode_bound", "mi_rtj_encode_frames",
-           "mi_rtj_get_tables", "mi_rtj_yuv420_to_rgb", "mi_rtj_encode_stream", "mi_rtj_decode_nocopy",
-           "mi_rtj_copy_ceiling", "mi_rtj_plan_spec_stats", "mi_rtj_plan_spec_lead", "mi_rtj_plan_decode_form", "mi_rtj_plan_overlapped",
-           "mi_rtj_plan_step_times", "mi_rtj_pipe_create", "mi_rtj_pipe_destroy", "mi_rtj_pipe_room",
-           "mi_rtj_pipe_pending", "mi_rtj_pipe_submit", "mi_rtj_pipe_next", "mi_rtj_pipe_peek_tag", "mi_rtj_pipe_flush",
-           "mi_rtj_pipe_profile", "mi_rtj_pipe_times", "mi_rtj_plan_set_runs", "mi_rtj_plan_run_times",
-           "mi_rtj_plan_run_stats", "mi_rtj_set_format", "mi_rtj_get_format", "mi_rtj_yuv422_to_rgb24",
-           "mi_rtj_encode_bound_fmt", "mi_rtj_encode_frames_fmt", "mi_rtj_encode_stream_fmt", "mi_rtj_plan_set_runs_fmt"]
+# every function of include/mi_rtjpeg.h, in its order: (what it returns, what it takes)
+SIGNATURES = {
+    "mi_rtj_device_count": (cint, []),
+    "mi_rtj_create": (vp, [cint]),
+    "mi_rtj_destroy": (None, [vp]),
+    "mi_rtj_last_error": (C.c_char_p, [vp]),
+    "mi_rtj_set_format": (cint, [vp, cint]),
+    "mi_rtj_get_format": (cint, [vp]),
+    "mi_rtj_decode": (cint, [vp, u8p, sz, u8pp, intp, cint, cint]),
+    "mi_rtj_decode_nocopy": (cint, [vp, u8p, sz, u8pp, intp]),
+    "mi_rtj_pipe_create": (vp, [vp, cint, cint, cint]),
+    "mi_rtj_pipe_destroy": (None, [vp]),
+    "mi_rtj_pipe_room": (cint, [vp]),
+    "mi_rtj_pipe_pending": (cint, [vp]),
+    "mi_rtj_pipe_submit": (cint, [vp, u8p, sz, u64]),
+    "mi_rtj_pipe_next": (cint, [vp, u8pp, intp, intp, intp, u64p]),
+    "mi_rtj_pipe_peek_tag": (cint, [vp, u64p]),
+    "mi_rtj_pipe_flush": (cint, [vp]),
+    "mi_rtj_pipe_profile": (cint, [vp, cint]),
+    "mi_rtj_pipe_times": (cint, [vp, f32p, intp]),
+    "mi_rtj_get_state": (None, [vp, intp, intp, intp]),
+    "mi_rtj_dev_alloc": (vp, [vp, sz]),
+    "mi_rtj_dev_free": (None, [vp, vp]),
+    "mi_rtj_h2d": (cint, [vp, vp, vp, sz]),
+    "mi_rtj_d2h": (cint, [vp, vp, vp, sz]),
+    "mi_rtj_dev_memset": (cint, [vp, vp, cint, sz]),
+    "mi_rtj_sync": (cint, [vp]),
+    "mi_rtj_plan_create": (vp, [vp, cint, u8p, u64p, u32p, u64p]),
+    "mi_rtj_plan_destroy": (None, [vp]),
+    "mi_rtj_plan_decode": (cint, [vp, vp, vp]),
+    "mi_rtj_plan_info": (None, [vp, intp, u64p, u64p, u64p]),
+    "mi_rtj_plan_profile": (None, [vp, cint]),
+    "mi_rtj_plan_times": (cint, [vp, f32p, intp]),
+    "mi_rtj_plan_step_times": (cint, [vp, f32p, cint, intp]),
+    "mi_rtj_plan_spec_stats": (cint, [vp, intp, i64p, i64p]),
+    "mi_rtj_plan_spec_lead": (cint, [vp, intp, intp]),
+    "mi_rtj_plan_decode_form": (cint, [vp, intp, intp, i64p]),
+    "mi_rtj_plan_overlapped": (cint, [vp]),
+    "mi_rtj_plan_set_runs": (cint, [vp, cint, intp]),
+    "mi_rtj_plan_set_runs_fmt": (cint, [vp, cint, intp]),
+    "mi_rtj_plan_run_times": (cint, [vp, f32p, intp]),
+    "mi_rtj_plan_run_stats": (cint, [vp, i64p]),
+    "mi_rtj_plan_read_index": (cint, [vp, u32p, sz]),
+    "mi_rtj_synth_frames": (cint, [vp, cint, cint, cint, cint, u32, cint, vp]),
+    "mi_rtj_synth_frames_lcg": (cint, [vp, cint, cint, cint, cint, u32, cint, vp]),
+    "mi_rtj_encode_bound": (sz, [cint, cint, cint, cint]),
+    "mi_rtj_encode_frames": (cint, [vp, cint, cint, cint, cint, vp, vp, cint, u64p, u32p]),
+    "mi_rtj_encode_stream": (cint, [vp, cint, cint, cint, cint, cint, cint, cint, vp, vp, cint, u64p, u32p]),
+    "mi_rtj_encode_bound_fmt": (sz, [cint, cint, cint, cint, cint]),
+    "mi_rtj_encode_frames_fmt": (cint, [vp, cint, cint, cint, cint, cint, vp, vp, cint, u64p, u32p]),
+    "mi_rtj_encode_stream_fmt": (cint, [vp, cint, cint, cint, cint, cint, cint, cint, cint, vp, vp, cint, u64p, u32p]),
+    "mi_rtj_yuv420_to_rgb": (cint, [vp, cint, cint, cint, cint, vp, sz, vp, sz, sz]),
+    "mi_rtj_yuv422_to_rgb24": (cint, [vp, cint, cint, cint, vp, sz, vp, sz, sz]),
+    "mi_rtj_copy_ceiling": (cint, [vp, vp, vp, sz, cint, C.POINTER(C.c_double)]),
+    "mi_rtj_get_tables": (cint, [cint, C.POINTER(C.c_int32), intp, intp]),
+}
+EXPORTS = list(SIGNATURES)
+# MI_RTJ_LIB: an alternative build of the same library (A/B experiments under tools/)
+LIB = Library("libmi_rtjpeg.so", "MI_RTJ_LIB", "mi_rtj_", MiRtjError, SIGNATURES)
+lib_path, load = LIB.path, LIB.load
 
 # picture formats (mi_rtj_set_format): RTJ_YUV420 / RTJ_YUV422 / RTJ_RGB8 of the reference
 FMT_YUV420, FMT_YUV422, FMT_GREY = 0, 1, 2
@@ -54,83 +91,6 @@ def blocks_of(fmt, w, h):
 KERNELS = ("k_index_summarize", "k_index_resolve", "k_index_emit", "k_decode", "k_spec_walk", "k_spec_verify")
 
 
-def load():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    p = lib_path()
-    if not os.path.exists(p):
-        raise MiRtjError(f"{p} is missing: run `python gmerlin-avdecoder_amd/build.py` (there is no CPU path)")
-    L = C.CDLL(p)
-    vp = C.c_void_p
-    L.mi_rtj_device_count.restype = C.c_int
-    L.mi_rtj_create.argtypes = [C.c_int]
-    L.mi_rtj_create.restype = vp
-    L.mi_rtj_destroy.argtypes = [vp]
-    L.mi_rtj_last_error.argtypes = [vp]
-    L.mi_rtj_last_error.restype = C.c_char_p
-    L.mi_rtj_decode.argtypes = [vp, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int), C.c_int, C.c_int]
-    L.mi_rtj_decode_nocopy.argtypes = [vp, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int)]
-    L.mi_rtj_get_state.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.mi_rtj_set_format.argtypes = [vp, C.c_int]
-    L.mi_rtj_get_format.argtypes = [vp]
-    L.mi_rtj_yuv422_to_rgb24.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t]
-    L.mi_rtj_dev_alloc.argtypes = [vp, C.c_size_t]
-    L.mi_rtj_dev_alloc.restype = vp
-    L.mi_rtj_dev_free.argtypes = [vp, vp]
-    L.mi_rtj_h2d.argtypes = [vp, vp, vp, C.c_size_t]
-    L.mi_rtj_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-    L.mi_rtj_dev_memset.argtypes = [vp, vp, C.c_int, C.c_size_t]
-    L.mi_rtj_sync.argtypes = [vp]
-    L.mi_rtj_plan_create.argtypes = [vp, C.c_int, u8p, u64p, u32p, u64p]
-    L.mi_rtj_plan_create.restype = vp
-    L.mi_rtj_plan_destroy.argtypes = [vp]
-    L.mi_rtj_plan_decode.argtypes = [vp, vp, vp]
-    L.mi_rtj_plan_info.argtypes = [vp, C.POINTER(C.c_int), u64p, u64p, u64p]
-    L.mi_rtj_plan_profile.argtypes = [vp, C.c_int]
-    L.mi_rtj_plan_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    L.mi_rtj_plan_spec_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
-    L.mi_rtj_plan_spec_lead.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.mi_rtj_plan_decode_form.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
-    L.mi_rtj_plan_overlapped.argtypes = [vp]
-    L.mi_rtj_plan_step_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
-    L.mi_rtj_plan_set_runs.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
-    L.mi_rtj_plan_set_runs_fmt.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
-    L.mi_rtj_plan_run_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    L.mi_rtj_plan_run_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
-    L.mi_rtj_pipe_create.argtypes = [vp, C.c_int, C.c_int, C.c_int]
-    L.mi_rtj_pipe_create.restype = vp
-    L.mi_rtj_pipe_destroy.argtypes = [vp]
-    L.mi_rtj_pipe_destroy.restype = None
-    L.mi_rtj_pipe_room.argtypes = [vp]
-    L.mi_rtj_pipe_pending.argtypes = [vp]
-    L.mi_rtj_pipe_submit.argtypes = [vp, u8p, C.c_size_t, C.c_uint64]
-    L.mi_rtj_pipe_next.argtypes = [vp, C.POINTER(u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                   C.POINTER(C.c_uint64)]
-    L.mi_rtj_pipe_peek_tag.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.mi_rtj_pipe_flush.argtypes = [vp]
-    L.mi_rtj_pipe_profile.argtypes = [vp, C.c_int]
-    L.mi_rtj_pipe_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    L.mi_rtj_plan_read_index.argtypes = [vp, u32p, C.c_size_t]
-    L.mi_rtj_synth_frames.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, vp]
-    L.mi_rtj_encode_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-    L.mi_rtj_encode_bound.restype = C.c_size_t
-    L.mi_rtj_encode_frames.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, u64p, u32p]
-    L.mi_rtj_yuv420_to_rgb.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t,
-                                       C.c_size_t]
-    L.mi_rtj_encode_stream.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp,
-                                       C.c_int, u64p, u32p]
-    L.mi_rtj_encode_bound_fmt.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.mi_rtj_encode_bound_fmt.restype = C.c_size_t
-    L.mi_rtj_encode_frames_fmt.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, u64p, u32p]
-    L.mi_rtj_encode_stream_fmt.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
-                                           vp, C.c_int, u64p, u32p]
-    L.mi_rtj_get_tables.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.mi_rtj_copy_ceiling.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
-    _LIB = L
-    return L
-
-
 def device_count():
     return load().mi_rtj_device_count()
 
@@ -143,6 +103,12 @@ def get_tables(Q):
         raise MiRtjError(f"mi_rtj_get_tables({Q}) -> {rc}")
     a = np.array(t, dtype=np.int32)
     return a[:64], a[64:], lb8.value, cb8.value
+
+
+def _run_lengths(lengths):
+    """(how many runs, their lengths as the int array both set_runs calls take); [] or None: no runs"""
+    lengths = [int(x) for x in (lengths or [])]
+    return len(lengths), (C.c_int * max(len(lengths), 1))(*lengths)
 
 
 class Plan:
@@ -217,16 +183,12 @@ class Plan:
     def set_runs(self, lengths):
         """Cut the plan into runs of consecutive pictures of one stream (include/mi_rtjpeg.h, "runs"); [] or None:
         independent pictures again.  Raises MiRtjError (and leaves the plan as it was) on a refused cut."""
-        lengths = [int(x) for x in (lengths or [])]
-        arr = (C.c_int * max(len(lengths), 1))(*lengths)
-        self.owner._chk(self.owner.L.mi_rtj_plan_set_runs(self.h, len(lengths), arr))
+        self.owner._chk(self.owner.L.mi_rtj_plan_set_runs(self.h, *_run_lengths(lengths)))
 
     def set_runs_fmt(self, lengths):
         """set_runs for a plan of any format (mi_rtj_plan_set_runs_fmt): on a 4:2:0 plan it is set_runs; on a 4:2:2 or
         greyscale plan "block b" of the run rule is in the format's stream order.  Same errors, same queries."""
-        lengths = [int(x) for x in (lengths or [])]
-        arr = (C.c_int * max(len(lengths), 1))(*lengths)
-        self.owner._chk(self.owner.L.mi_rtj_plan_set_runs_fmt(self.h, len(lengths), arr))
+        self.owner._chk(self.owner.L.mi_rtj_plan_set_runs_fmt(self.h, *_run_lengths(lengths)))
 
     def run_times(self):
         """(ms of the run kernels summed over the decodes since profile(True), decodes that ran them)."""
@@ -254,7 +216,7 @@ class Pipe:
         self.owner = owner
         self.h = owner.L.mi_rtj_pipe_create(owner.h, depth, coded_w, coded_h)
         if not self.h:
-            raise MiRtjError("mi_rtj_pipe_create failed: " + owner.L.mi_rtj_last_error(owner.h).decode())
+            raise MiRtjError("mi_rtj_pipe_create failed: " + owner.last_error())
 
     def close(self):
         if self.h:
@@ -303,29 +265,25 @@ class Pipe:
         return dict(zip(KERNELS, [float(x) for x in ms])), n.value
 
 
-class MiRtj:
+class MiRtj(Device):
     """One decoder instance (== one RTjpeg_t of the reference) bound to one device."""
+    LIB = LIB
 
     def __init__(self, device=-1):
-        self.L = load()
         self._plans = weakref.WeakSet()
-        self.h = self.L.mi_rtj_create(device)
-        if not self.h:
-            raise MiRtjError("mi_rtj_create failed: " + self.L.mi_rtj_last_error(None).decode())
+        super().__init__(device)
+
+    def _error(self, text, rc, what):
+        return MiRtjError({"create": "mi_rtj_create failed: ", "alloc": "alloc failed: "}.get(what, f"rc={rc}: ") + text)
 
     def close(self):
         if getattr(self, "h", None):
             for p in list(self._plans):  # a plan must not outlive its instance
                 p.close()
-            self.L.mi_rtj_destroy(self.h)
-            self.h = None
+        super().close()
 
     def __del__(self):
         self.close()
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise MiRtjError(f"rc={rc}: " + self.L.mi_rtj_last_error(self.h).decode())
 
     # -- picture format (RTjpeg_set_format) --
     def set_format(self, fmt):
@@ -390,30 +348,8 @@ class MiRtj:
         self.L.mi_rtj_get_state(self.h, C.byref(w), C.byref(h), C.byref(q))
         return w.value, h.value, q.value
 
-    # -- device memory --
-    def alloc(self, nbytes):
-        p = self.L.mi_rtj_dev_alloc(self.h, nbytes)
-        if not p:
-            raise MiRtjError("alloc failed: " + self.L.mi_rtj_last_error(self.h).decode())
-        return p
-
-    def free(self, p):
-        self.L.mi_rtj_dev_free(self.h, p)
-
-    def h2d(self, dptr, arr, offset=0):
-        arr = np.ascontiguousarray(arr)
-        self._chk(self.L.mi_rtj_h2d(self.h, dptr + offset, arr.ctypes.data, arr.nbytes))
-
-    def d2h(self, dptr, nbytes, offset=0, dtype=np.uint8):
-        a = np.empty(nbytes // np.dtype(dtype).itemsize, dtype=dtype)
-        self._chk(self.L.mi_rtj_d2h(self.h, a.ctypes.data, dptr + offset, nbytes))
-        return a
-
     def memset(self, dptr, value, nbytes, offset=0):
         self._chk(self.L.mi_rtj_dev_memset(self.h, dptr + offset, value, nbytes))
-
-    def sync(self):
-        self._chk(self.L.mi_rtj_sync(self.h))
 
     # -- batches --
     def plan(self, headers, pkt_offset, pkt_len, out_offset):
@@ -426,7 +362,7 @@ class MiRtj:
         h = self.L.mi_rtj_plan_create(self.h, n, headers.ctypes.data_as(u8p), po.ctypes.data_as(u64p),
                                       pl.ctypes.data_as(u32p), oo.ctypes.data_as(u64p))
         if not h:
-            raise MiRtjError("plan_create failed: " + self.L.mi_rtj_last_error(self.h).decode())
+            raise MiRtjError("plan_create failed: " + self.last_error())
         return Plan(self, h, n)
 
     def upload_packets(self, pkts, align=1):
@@ -472,7 +408,6 @@ class MiRtj:
         """SURVEY 8d's generator: LCG noise, one sequence over all frames (see include/mi_rtjpeg.h)"""
         fsz = w * h * 3 // 2
         d = dptr if dptr is not None else self.alloc(fsz * n)
-        self.L.mi_rtj_synth_frames_lcg.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p]
         self._chk(self.L.mi_rtj_synth_frames_lcg(self.h, w, h, first, n, seed, amp, d))
         return d
 

@@ -1,13 +1,12 @@
 """ctypes view of include/mi_dv.h (libmi_dv.so, the DV decoder and encoder: 525/60 4:1:1, 625/50 4:2:0 and 625/50 4:1:1 at
 25 Mbit/s, both line systems in 4:2:2 at 50 Mbit/s).  No CPU path: without the library or a gfx950 device construction raises MiDvError with
 the library's own message."""
-import contextlib
 import ctypes as C
-import os
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from ._capi import Device, Library, cint, f32p, i64, i64p, intp, sz, u8p, u8pp, uint, vp
+
 FRAME_BYTES, PICTURE_BYTES, W, H, CW = 120000, 720 * 480 * 3 // 2, 720, 480, 180
 SYS_525_60, SYS_625_50 = 0, 1
 FRAME_BYTES_625, PICTURE_BYTES_625, H_625, CW_625, CH_625 = 144000, 720 * 576 + 2 * 360 * 288, 576, 360, 288
@@ -22,89 +21,62 @@ GEOMETRY = {SYS_525_60: (FRAME_BYTES, PICTURE_BYTES, ((W, H), (CW, H), (CW, H)))
             SYS_625_50_411: (FRAME_BYTES_625, PICTURE_BYTES_625_411, ((W, H_625), (CW_625_411, H_625), (CW_625_411, H_625))),
             SYS_525_60_422: (FRAME_BYTES_525_422, PICTURE_BYTES_525_422, ((W, H), (CW_422, H), (CW_422, H))),
             SYS_625_50_422: (FRAME_BYTES_625_422, PICTURE_BYTES_625_422, ((W, H_625), (CW_422, H_625), (CW_422, H_625)))}
-EXPORTS = ["mi_dv_device_count", "mi_dv_create", "mi_dv_destroy", "mi_dv_last_error", "mi_dv_dev_alloc", "mi_dv_dev_free",
-           "mi_dv_h2d", "mi_dv_d2h", "mi_dv_sync", "mi_dv_decode_batch", "mi_dv_kernel_times", "mi_dv_decode_frame",
-           "mi_dv_copy_tables", "mi_dv_system_of", "mi_dv_decode_batch_sys", "mi_dv_decode_frame_sys", "mi_dv_mb_place",
-           "mi_dv_profile_of", "mi_dv_kind_of", "mi_dv_mb_rects", "mi_dv_held_macroblocks", "mi_dv_decode_batch_held",
-           "mi_dv_hold_stats", "mi_dv_hold_times", "mi_dv_decode_frame_held", "mi_dv_hold_reset", "mi_dv_encode_batch",
-           "mi_dv_encode_frame", "mi_dv_encode_times", "mi_dv_encode_stats", "mi_dv_audio_batch", "mi_dv_audio_write_batch",
-           "mi_dv_audio_samples", "mi_dv_audio_times", "mi_dv_audio_copy_tables", "mi_dv_meta_batch", "mi_dv_meta_write_batch",
-           "mi_dv_timecode_of", "mi_dv_meta_times"]
 META_INTS = 16  # include/mi_dv.h: MI_DV_META_INTS; the row: found mask, timecode h m s f, drop, y m d, h m s, wide, raw x 3
 META_HAS_TIMECODE, META_HAS_DATE, META_HAS_TIME, META_HAS_CONTROL = 1, 2, 4, 8
 AUDIO_PAIRS, AUDIO_PAIR_BYTES = 4, 8192  # include/mi_dv.h: MI_DV_AUDIO_PAIRS, MI_DV_AUDIO_PAIR_BYTES
 AUDIO_CHANNELS = {SYS_525_60: 1, SYS_625_50: 1, SYS_625_50_411: 1, SYS_525_60_422: 2, SYS_625_50_422: 2}  # DIF channels
 STA_ERRORS = 0x8080  # the default mask of held macroblocks: STA 0111 and 1111 (include/mi_dv.h: MI_DV_STA_ERRORS)
-_LIB = None
-u8p = C.POINTER(C.c_uint8)
 
 
 class MiDvError(RuntimeError):
     pass
 
 
-def lib_path():
-    return os.environ.get("MI_DV_LIB") or os.path.join(HERE, "lib", "libmi_dv.so")
-
-
-def load():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    p = lib_path()
-    if not os.path.exists(p):
-        raise MiDvError(f"{p} is missing: run `python gmerlin-avdecoder_amd/build.py` (there is no CPU path)")
-    L = C.CDLL(p)
-    vp = C.c_void_p
-    L.mi_dv_device_count.restype = C.c_int
-    L.mi_dv_create.argtypes = [C.c_int]
-    L.mi_dv_create.restype = vp
-    L.mi_dv_destroy.argtypes = [vp]
-    L.mi_dv_destroy.restype = None
-    L.mi_dv_last_error.argtypes = [vp]
-    L.mi_dv_last_error.restype = C.c_char_p
-    L.mi_dv_dev_alloc.argtypes = [vp, C.c_size_t]
-    L.mi_dv_dev_alloc.restype = vp
-    L.mi_dv_dev_free.argtypes = [vp, vp]
-    L.mi_dv_dev_free.restype = None
-    L.mi_dv_h2d.argtypes = [vp, vp, vp, C.c_size_t]
-    L.mi_dv_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-    L.mi_dv_sync.argtypes = [vp]
-    L.mi_dv_decode_batch.argtypes = [vp, vp, C.c_int, vp]
-    L.mi_dv_kernel_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    L.mi_dv_decode_frame.argtypes = [vp, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int)]
-    L.mi_dv_copy_tables.argtypes = [vp, C.c_size_t]
-    L.mi_dv_copy_tables.restype = C.c_size_t
-    L.mi_dv_system_of.argtypes = [u8p, C.c_size_t]
-    L.mi_dv_profile_of.argtypes = [u8p, C.c_size_t]
-    L.mi_dv_kind_of.argtypes = [u8p, C.c_size_t]
-    L.mi_dv_decode_batch_sys.argtypes = [vp, C.c_int, vp, C.c_int, vp]
-    L.mi_dv_decode_frame_sys.argtypes = [vp, C.c_int, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int)]
-    L.mi_dv_mb_place.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2
-    L.mi_dv_mb_rects.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int * 4)]
-    L.mi_dv_held_macroblocks.argtypes = [C.c_int, u8p, C.c_size_t, C.c_uint]
-    L.mi_dv_decode_batch_held.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int), vp, C.c_uint]
-    L.mi_dv_hold_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
-    L.mi_dv_hold_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    L.mi_dv_decode_frame_held.argtypes = [vp, C.c_int, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int), C.c_uint,
-                                          C.POINTER(C.c_int)]
-    L.mi_dv_hold_reset.argtypes = [vp]
-    L.mi_dv_encode_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int]
-    L.mi_dv_encode_frame.argtypes = [vp, C.c_int, C.POINTER(u8p), C.POINTER(C.c_int), u8p, C.c_size_t, C.c_int]
-    L.mi_dv_encode_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    L.mi_dv_encode_stats.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
-    L.mi_dv_audio_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]
-    L.mi_dv_audio_write_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_int)]
-    L.mi_dv_audio_samples.argtypes = [C.c_int, C.c_int, C.c_longlong]
-    L.mi_dv_audio_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    L.mi_dv_audio_copy_tables.argtypes = [vp, C.c_size_t]
-    L.mi_dv_audio_copy_tables.restype = C.c_size_t
-    L.mi_dv_meta_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp]
-    L.mi_dv_meta_write_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_int]
-    L.mi_dv_timecode_of.argtypes = [C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_int)]
-    L.mi_dv_meta_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    _LIB = L
-    return L
+# every function of include/mi_dv.h, in its order: (what it returns, what it takes)
+SIGNATURES = {
+    "mi_dv_device_count": (cint, []),
+    "mi_dv_create": (vp, [cint]),
+    "mi_dv_destroy": (None, [vp]),
+    "mi_dv_last_error": (C.c_char_p, [vp]),
+    "mi_dv_dev_alloc": (vp, [vp, sz]),
+    "mi_dv_dev_free": (None, [vp, vp]),
+    "mi_dv_h2d": (cint, [vp, vp, vp, sz]),
+    "mi_dv_d2h": (cint, [vp, vp, vp, sz]),
+    "mi_dv_sync": (cint, [vp]),
+    "mi_dv_decode_batch": (cint, [vp, vp, cint, vp]),
+    "mi_dv_kernel_times": (cint, [vp, f32p, intp]),
+    "mi_dv_decode_frame": (cint, [vp, u8p, sz, u8pp, intp]),
+    "mi_dv_copy_tables": (sz, [vp, sz]),
+    "mi_dv_system_of": (cint, [u8p, sz]),
+    "mi_dv_profile_of": (cint, [u8p, sz]),
+    "mi_dv_kind_of": (cint, [u8p, sz]),
+    "mi_dv_decode_batch_sys": (cint, [vp, cint, vp, cint, vp]),
+    "mi_dv_decode_frame_sys": (cint, [vp, cint, u8p, sz, u8pp, intp]),
+    "mi_dv_mb_place": (cint, [cint, cint, cint, cint, intp, intp]),
+    "mi_dv_mb_rects": (cint, [cint, cint, cint, cint, C.POINTER(C.c_int * 4)]),
+    "mi_dv_held_macroblocks": (cint, [cint, u8p, sz, uint]),
+    "mi_dv_decode_batch_held": (cint, [vp, cint, vp, cint, vp, cint, intp, vp, uint]),
+    "mi_dv_hold_stats": (cint, [vp, i64p]),
+    "mi_dv_hold_times": (cint, [vp, f32p, intp]),
+    "mi_dv_decode_frame_held": (cint, [vp, cint, u8p, sz, u8pp, intp, uint, intp]),
+    "mi_dv_hold_reset": (cint, [vp]),
+    "mi_dv_encode_batch": (cint, [vp, cint, vp, cint, vp, cint]),
+    "mi_dv_encode_frame": (cint, [vp, cint, u8pp, intp, u8p, sz, cint]),
+    "mi_dv_encode_times": (cint, [vp, f32p, intp]),
+    "mi_dv_encode_stats": (cint, [vp, i64p, i64p]),
+    "mi_dv_audio_batch": (cint, [vp, cint, vp, cint, vp, cint, vp]),
+    "mi_dv_audio_write_batch": (cint, [vp, cint, vp, cint, vp, cint, cint, intp]),
+    "mi_dv_audio_samples": (cint, [cint, cint, i64]),
+    "mi_dv_audio_times": (cint, [vp, f32p, intp]),
+    "mi_dv_audio_copy_tables": (sz, [vp, sz]),
+    "mi_dv_meta_batch": (cint, [vp, cint, vp, cint, vp]),
+    "mi_dv_meta_write_batch": (cint, [vp, cint, vp, cint, i64, cint, i64, cint]),
+    "mi_dv_timecode_of": (cint, [cint, i64, cint, intp]),
+    "mi_dv_meta_times": (cint, [vp, f32p, intp]),
+}
+EXPORTS = list(SIGNATURES)
+LIB = Library("libmi_dv.so", "MI_DV_LIB", "mi_dv_", MiDvError, SIGNATURES)
+lib_path, load = LIB.path, LIB.load
 
 
 def tables():
@@ -213,57 +185,8 @@ def held_macroblocks(frame, system, sta_mask=0):
     return n
 
 
-class MiDv:
-    def __init__(self, device=-1):
-        self.L = load()
-        self.c = self.L.mi_dv_create(device)
-        if not self.c:
-            raise MiDvError(self.L.mi_dv_last_error(None).decode())
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise MiDvError(self.L.mi_dv_last_error(self.c).decode())
-
-    def alloc(self, n):
-        d = self.L.mi_dv_dev_alloc(self.c, n)
-        if not d:
-            raise MiDvError(self.L.mi_dv_last_error(self.c).decode())
-        return d
-
-    def free(self, d):
-        self.L.mi_dv_dev_free(self.c, d)
-
-    def h2d(self, d, a, offset=0):
-        a = np.ascontiguousarray(a)
-        self._chk(self.L.mi_dv_h2d(self.c, d + offset, a.ctypes.data, a.nbytes))
-
-    def d2h(self, d, n, offset=0):
-        a = np.empty(n, np.uint8)
-        self._chk(self.L.mi_dv_d2h(self.c, a.ctypes.data, d + offset, n))
-        return a
-
-    def sync(self):
-        self._chk(self.L.mi_dv_sync(self.c))
-
-    def _times(self, fn):
-        ms, n = C.c_float(), C.c_int()
-        self._chk(fn(self.c, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-    @contextlib.contextmanager
-    def _resident(self, *what):
-        """device buffers for the length of a with block: an array is uploaded, an int is a size in bytes, None stays None"""
-        ds = []
-        try:
-            for a in what:
-                ds.append(None if a is None else self.alloc(a if isinstance(a, int) else a.nbytes))
-                if isinstance(a, np.ndarray):
-                    self.h2d(ds[-1], a)
-            yield ds
-        finally:
-            for d in ds:
-                if d:
-                    self.free(d)
+class MiDv(Device):
+    LIB = LIB
 
     @staticmethod
     def _planes(system, strides, planes=None):
@@ -477,8 +400,3 @@ class MiDv:
     def meta_times(self):
         """(total milliseconds, launches) of k_dv_meta_extract and k_dv_meta_write since the last call"""
         return self._times(self.L.mi_dv_meta_times)
-
-    def close(self):
-        if self.c:
-            self.L.mi_dv_destroy(self.c)
-            self.c = None

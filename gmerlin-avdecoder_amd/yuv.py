@@ -2,22 +2,16 @@
 yv12, YV12, YVU9, v308, v408, v410, v210, yuv4).  No CPU path: without the library or a gfx950 device construction raises
 MiYuvError with the library's own message; codec_of, layout_of and alpha_v408 are host-side and need no device."""
 import collections
-import contextlib
 import ctypes as C
-import os
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from ._capi import Device, Library, cint, f32p, intp, sz, u8p, u8pp, u32, vp
+
 YUV2, TWOVUY, YV12_LOWER, YV12_UPPER, VYUY, YVU9, V308, V408, V410, V210, YUV4 = range(11)
 CODECS = {"yuv2": YUV2, "2vuy": TWOVUY, "yv12": YV12_LOWER, "YV12": YV12_UPPER, "VYUY": VYUY, "YVU9": YVU9, "v308": V308,
           "v408": V408, "v410": V410, "v210": V210, "yuv4": YUV4}
 OK, ERR_ARG, ERR_HIP, ERR_NOMEM, ERR_FORMAT = 0, -1, -2, -3, -4
-EXPORTS = ["mi_yuv_device_count", "mi_yuv_create", "mi_yuv_destroy", "mi_yuv_last_error", "mi_yuv_dev_alloc", "mi_yuv_dev_free",
-           "mi_yuv_h2d", "mi_yuv_d2h", "mi_yuv_sync", "mi_yuv_codec_of", "mi_yuv_layout_of", "mi_yuv_alpha_v408",
-           "mi_yuv_unpack_batch", "mi_yuv_unpack_frame", "mi_yuv_times"]
-_LIB = None
-u8p = C.POINTER(C.c_uint8)
 
 
 class MiYuvError(RuntimeError):
@@ -35,41 +29,27 @@ class _Layout(C.Structure):
 Layout = collections.namedtuple("Layout", "packet_bytes picture_bytes packet_strides planes")
 
 
-def lib_path():
-    return os.environ.get("MI_YUV_LIB") or os.path.join(HERE, "lib", "libmi_yuv.so")
-
-
-def load():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    p = lib_path()
-    if not os.path.exists(p):
-        raise MiYuvError(f"{p} is missing: run `python gmerlin-avdecoder_amd/build.py` (there is no CPU path)")
-    L = C.CDLL(p)
-    vp = C.c_void_p
-    L.mi_yuv_device_count.restype = C.c_int
-    L.mi_yuv_create.argtypes = [C.c_int]
-    L.mi_yuv_create.restype = vp
-    L.mi_yuv_destroy.argtypes = [vp]
-    L.mi_yuv_destroy.restype = None
-    L.mi_yuv_last_error.argtypes = [vp]
-    L.mi_yuv_last_error.restype = C.c_char_p
-    L.mi_yuv_dev_alloc.argtypes = [vp, C.c_size_t]
-    L.mi_yuv_dev_alloc.restype = vp
-    L.mi_yuv_dev_free.argtypes = [vp, vp]
-    L.mi_yuv_dev_free.restype = None
-    L.mi_yuv_h2d.argtypes = [vp, vp, vp, C.c_size_t]
-    L.mi_yuv_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-    L.mi_yuv_sync.argtypes = [vp]
-    L.mi_yuv_codec_of.argtypes = [C.c_uint32]
-    L.mi_yuv_layout_of.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(_Layout)]
-    L.mi_yuv_alpha_v408.argtypes = [u8p]
-    L.mi_yuv_unpack_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_size_t]
-    L.mi_yuv_unpack_frame.argtypes = [vp, C.c_int, C.c_int, C.c_int, u8p, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_int)]
-    L.mi_yuv_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    _LIB = L
-    return L
+# every function of include/mi_yuv.h, in its order: (what it returns, what it takes)
+SIGNATURES = {
+    "mi_yuv_device_count": (cint, []),
+    "mi_yuv_create": (vp, [cint]),
+    "mi_yuv_destroy": (None, [vp]),
+    "mi_yuv_last_error": (C.c_char_p, [vp]),
+    "mi_yuv_dev_alloc": (vp, [vp, sz]),
+    "mi_yuv_dev_free": (None, [vp, vp]),
+    "mi_yuv_h2d": (cint, [vp, vp, vp, sz]),
+    "mi_yuv_d2h": (cint, [vp, vp, vp, sz]),
+    "mi_yuv_sync": (cint, [vp]),
+    "mi_yuv_codec_of": (cint, [u32]),
+    "mi_yuv_layout_of": (cint, [cint, cint, cint, C.POINTER(_Layout)]),
+    "mi_yuv_alpha_v408": (cint, [u8p]),
+    "mi_yuv_unpack_batch": (cint, [vp, cint, cint, cint, vp, sz, cint, vp, sz]),
+    "mi_yuv_unpack_frame": (cint, [vp, cint, cint, cint, u8p, sz, u8pp, intp]),
+    "mi_yuv_times": (cint, [vp, f32p, intp]),
+}
+EXPORTS = list(SIGNATURES)
+LIB = Library("libmi_yuv.so", "MI_YUV_LIB", "mi_yuv_", MiYuvError, SIGNATURES)
+lib_path, load = LIB.path, LIB.load
 
 
 def codec_of(fourcc):
@@ -109,51 +89,11 @@ def up16(n):
     return (n + 15) // 16 * 16
 
 
-class MiYuv:
-    def __init__(self, device=-1):
-        self.L = load()
-        self.c = self.L.mi_yuv_create(device)
-        if not self.c:
-            raise MiYuvError(self.L.mi_yuv_last_error(None).decode(), ERR_HIP)
+class MiYuv(Device):
+    LIB = LIB
 
-    def _chk(self, rc):
-        if rc != 0:
-            raise MiYuvError(self.L.mi_yuv_last_error(self.c).decode(), rc)
-
-    def alloc(self, n):
-        d = self.L.mi_yuv_dev_alloc(self.c, n)
-        if not d:
-            raise MiYuvError(self.L.mi_yuv_last_error(self.c).decode(), ERR_NOMEM)
-        return d
-
-    def free(self, d):
-        self.L.mi_yuv_dev_free(self.c, d)
-
-    def h2d(self, d, a, offset=0):
-        a = np.ascontiguousarray(a)
-        self._chk(self.L.mi_yuv_h2d(self.c, d + offset, a.ctypes.data, a.nbytes))
-
-    def d2h(self, d, n, offset=0):
-        a = np.empty(n, np.uint8)
-        self._chk(self.L.mi_yuv_d2h(self.c, a.ctypes.data, d + offset, n))
-        return a
-
-    def sync(self):
-        self._chk(self.L.mi_yuv_sync(self.c))
-
-    @contextlib.contextmanager
-    def _resident(self, *what):
-        """device buffers for the length of a with block: an array is uploaded, an int is a size in bytes"""
-        ds = []
-        try:
-            for a in what:
-                ds.append(self.alloc(a if isinstance(a, int) else a.nbytes))
-                if isinstance(a, np.ndarray):
-                    self.h2d(ds[-1], a)
-            yield ds
-        finally:
-            for d in ds:
-                self.free(d)
+    def _error(self, text, rc, what):
+        return MiYuvError(text, {"create": ERR_HIP, "alloc": ERR_NOMEM}.get(what, rc))
 
     def unpack_batch(self, codec, w, h, d_packets, packet_stride, n, d_pics, pic_stride):
         """packet i at d_packets + i * packet_stride -> picture i at d_pics + i * pic_stride, one launch queued on the
@@ -189,11 +129,4 @@ class MiYuv:
 
     def times(self):
         """(total milliseconds, launches) of the unpack kernels since the last call"""
-        ms, n = C.c_float(), C.c_int()
-        self._chk(self.L.mi_yuv_times(self.c, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-    def close(self):
-        if self.c:
-            self.L.mi_yuv_destroy(self.c)
-            self.c = None
+        return self._times(self.L.mi_yuv_times)
