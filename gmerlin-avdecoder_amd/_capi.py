@@ -1,6 +1,6 @@
-"""What the ctypes views of the three libraries (binding.py, dv.py, yuv.py) share: a Library opens one shared object and
-gives its functions the signatures of a table kept as plain data, a Device is the part of MiRtj, MiDv and MiYuv that
-the three C interfaces spell alike (include/*.h: create, destroy, last_error, dev_alloc, dev_free, h2d, d2h, sync)."""
+"""What the ctypes views of the four libraries (binding.py, dv.py, yuv.py, rgb.py) share: a Library opens one shared object
+and gives its functions the signatures of a table kept as plain data, a Device is the part of MiRtj, MiDv, MiYuv and MiRgb
+that the four C interfaces spell alike (include/*.h: create, destroy, last_error, dev_alloc, dev_free, h2d, d2h, sync)."""
 import contextlib
 import ctypes as C
 import os

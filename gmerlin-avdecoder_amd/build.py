@@ -97,6 +97,20 @@ def build_yuv(force=False, verbose=False):
     return YUV_LIB
 
 
+RGB_LIB = os.path.join(LIBDIR, "libmi_rgb.so")
+
+
+def build_rgb(force=False, verbose=False):
+    """libmi_rgb.so: the raw RGB family of QuickTime and AVI (include/mi_rgb.h), gfx950.  The rule is csrc/Makefile's."""
+    cmd = ["make", "-C", CSRC, "HIPCC=" + HIPCC, RGB_LIB] + (["-B"] if force else [])
+    if verbose:
+        print(" ".join(cmd))
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("make libmi_rgb.so failed:\n" + r.stdout + r.stderr)
+    return RGB_LIB
+
+
 TEST_VARIANT = os.path.join(LIBDIR, "libmi_rtjpeg_generic_paths.so")
 
 
@@ -143,5 +157,6 @@ if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_dv(force="--force" in sys.argv, verbose=True))
     print(build_yuv(force="--force" in sys.argv, verbose=True))
+    print(build_rgb(force="--force" in sys.argv, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=True))

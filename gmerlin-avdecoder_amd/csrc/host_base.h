@@ -1,8 +1,8 @@
-// host_base.h — the host layer the device libraries share (libmi_rtjpeg.so, libmi_dv.so, libmi_yuv.so): memory, streams
-// and events that free themselves, the base of an instance, how an error becomes a code and a text, the checked HIP
-// call, buffers that only grow, the event timer around a launch, and the bodies of the entry points every library has.
-// Host only; depends on HIP and the standard library, on none of the public headers.  Each library is one translation
-// unit that includes this once: what the anonymous namespace holds is one per .so.
+// host_base.h — the host layer the device libraries share (libmi_rtjpeg.so, libmi_dv.so, libmi_yuv.so, libmi_rgb.so):
+// memory, streams and events that free themselves, the base of an instance, how an error becomes a code and a text, the
+// checked HIP call, buffers that only grow, the event timer around a launch, and the bodies of the entry points every
+// library has.  Host only; depends on HIP and the standard library, on none of the public headers.  Each library is one
+// translation unit that includes this once: what the anonymous namespace holds is one per .so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
