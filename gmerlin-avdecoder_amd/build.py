@@ -111,6 +111,20 @@ def build_rgb(force=False, verbose=False):
     return RGB_LIB
 
 
+TGA_LIB = os.path.join(LIBDIR, "libmi_tga.so")
+
+
+def build_tga(force=False, verbose=False):
+    """libmi_tga.so: Targa packets, run-length included (include/mi_tga.h), gfx950.  The rule is csrc/Makefile's."""
+    cmd = ["make", "-C", CSRC, "HIPCC=" + HIPCC, TGA_LIB] + (["-B"] if force else [])
+    if verbose:
+        print(" ".join(cmd))
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("make libmi_tga.so failed:\n" + r.stdout + r.stderr)
+    return TGA_LIB
+
+
 TEST_VARIANT = os.path.join(LIBDIR, "libmi_rtjpeg_generic_paths.so")
 
 
@@ -158,5 +172,6 @@ if __name__ == "__main__":
     print(build_dv(force="--force" in sys.argv, verbose=True))
     print(build_yuv(force="--force" in sys.argv, verbose=True))
     print(build_rgb(force="--force" in sys.argv, verbose=True))
+    print(build_tga(force="--force" in sys.argv, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=True))
