@@ -125,6 +125,20 @@ def build_tga(force=False, verbose=False):
     return TGA_LIB
 
 
+SPU_LIB = os.path.join(LIBDIR, "libmi_spu.so")
+
+
+def build_spu(force=False, verbose=False):
+    """libmi_spu.so: DVD subpictures (include/mi_spu.h), gfx950.  The rule is csrc/Makefile's."""
+    cmd = ["make", "-C", CSRC, "HIPCC=" + HIPCC, SPU_LIB] + (["-B"] if force else [])
+    if verbose:
+        print(" ".join(cmd))
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("make libmi_spu.so failed:\n" + r.stdout + r.stderr)
+    return SPU_LIB
+
+
 TEST_VARIANT = os.path.join(LIBDIR, "libmi_rtjpeg_generic_paths.so")
 
 
@@ -173,5 +187,6 @@ if __name__ == "__main__":
     print(build_yuv(force="--force" in sys.argv, verbose=True))
     print(build_rgb(force="--force" in sys.argv, verbose=True))
     print(build_tga(force="--force" in sys.argv, verbose=True))
+    print(build_spu(force="--force" in sys.argv, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=True))
