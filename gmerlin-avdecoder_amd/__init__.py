@@ -1,6 +1,6 @@
 """MI355X-native decode paths for gmerlin-avdecoder.
 
-The product is six libraries under csrc/, each with a C ABI under include/, plus the C plugin wrappers that bind RTjpeg
+The product is seven libraries under csrc/, each with a C ABI under include/, plus the C plugin wrappers that bind RTjpeg
 and DV into the reference's bgav_video_decoder_t table.  This Python package is only the ctypes view of those ABIs used by
 tests/ and bench.py, one module per library on the base they share (_capi.py):
   binding  libmi_rtjpeg.so (mi_rtjpeg.h): RTjpeg decode, batch plans, pipelined sessions, the encoder
@@ -9,5 +9,6 @@ tests/ and bench.py, one module per library on the base they share (_capi.py):
   rgb      libmi_rgb.so (mi_rgb.h): the raw RGB family of QuickTime and AVI
   tga      libmi_tga.so (mi_tga.h): Targa packets, run-length included
   spu      libmi_spu.so (mi_spu.h): DVD subpictures
-The names below are RTjpeg's; dv, yuv, rgb, tga and spu are imported as modules."""
+  gsm      libmi_gsm.so (mi_gsm.h): GSM 06.10 and MS GSM audio
+The names below are RTjpeg's; dv, yuv, rgb, tga, spu and gsm are imported as modules."""
 from .binding import (MiRtj, MiRtjError, Plan, device_count, get_tables, lib_path, load)  # noqa: F401

@@ -139,6 +139,20 @@ def build_spu(force=False, verbose=False):
     return SPU_LIB
 
 
+GSM_LIB = os.path.join(LIBDIR, "libmi_gsm.so")
+
+
+def build_gsm(force=False, verbose=False):
+    """libmi_gsm.so: GSM 06.10 and MS GSM audio (include/mi_gsm.h), gfx950.  The rule is csrc/Makefile's."""
+    cmd = ["make", "-C", CSRC, "HIPCC=" + HIPCC, GSM_LIB] + (["-B"] if force else [])
+    if verbose:
+        print(" ".join(cmd))
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("make libmi_gsm.so failed:\n" + r.stdout + r.stderr)
+    return GSM_LIB
+
+
 TEST_VARIANT = os.path.join(LIBDIR, "libmi_rtjpeg_generic_paths.so")
 
 
@@ -188,5 +202,6 @@ if __name__ == "__main__":
     print(build_rgb(force="--force" in sys.argv, verbose=True))
     print(build_tga(force="--force" in sys.argv, verbose=True))
     print(build_spu(force="--force" in sys.argv, verbose=True))
+    print(build_gsm(force="--force" in sys.argv, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=True))
