@@ -1,6 +1,6 @@
-"""What the ctypes views of the seven libraries (binding.py, dv.py, yuv.py, rgb.py, tga.py, spu.py, gsm.py) share: a Library
+"""What the ctypes views of the eight libraries (binding.py, dv.py, yuv.py, rgb.py, tga.py, spu.py, gsm.py, pcm.py) share: a Library
 opens one shared object and gives its functions the signatures of a table kept as plain data, a Device is the part of MiRtj,
-MiDv, MiYuv, MiRgb, MiTga, MiSpu and MiGsm that the seven C interfaces spell alike (include/*.h: create, destroy, last_error, dev_alloc, dev_free, h2d, d2h, sync)."""
+MiDv, MiYuv, MiRgb, MiTga, MiSpu, MiGsm and MiPcm that the eight C interfaces spell alike (include/*.h: create, destroy, last_error, dev_alloc, dev_free, h2d, d2h, sync)."""
 import contextlib
 import ctypes as C
 import os

@@ -153,6 +153,20 @@ def build_gsm(force=False, verbose=False):
     return GSM_LIB
 
 
+PCM_LIB = os.path.join(LIBDIR, "libmi_pcm.so")
+
+
+def build_pcm(force=False, verbose=False):
+    """libmi_pcm.so: the PCM family of lib/audio_pcm.c (include/mi_pcm.h), gfx950.  The rule is csrc/Makefile's."""
+    cmd = ["make", "-C", CSRC, "HIPCC=" + HIPCC, PCM_LIB] + (["-B"] if force else [])
+    if verbose:
+        print(" ".join(cmd))
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("make libmi_pcm.so failed:\n" + r.stdout + r.stderr)
+    return PCM_LIB
+
+
 TEST_VARIANT = os.path.join(LIBDIR, "libmi_rtjpeg_generic_paths.so")
 
 
@@ -203,5 +217,6 @@ if __name__ == "__main__":
     print(build_tga(force="--force" in sys.argv, verbose=True))
     print(build_spu(force="--force" in sys.argv, verbose=True))
     print(build_gsm(force="--force" in sys.argv, verbose=True))
+    print(build_pcm(force="--force" in sys.argv, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=True))

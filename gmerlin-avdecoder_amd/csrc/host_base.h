@@ -1,4 +1,4 @@
-// host_base.h — the host layer the device libraries share (libmi_rtjpeg.so, libmi_dv.so, libmi_yuv.so, libmi_rgb.so, libmi_tga.so, libmi_spu.so, libmi_gsm.so):
+// host_base.h — the host layer the device libraries share (libmi_rtjpeg.so, libmi_dv.so, libmi_yuv.so, libmi_rgb.so, libmi_tga.so, libmi_spu.so, libmi_gsm.so, libmi_pcm.so):
 // memory, streams and events that free themselves, the base of an instance, how an error becomes a code and a text, the
 // checked HIP call, buffers that only grow, the event timer around a launch, and the bodies of the entry points every
 // library has.  Host only; depends on HIP and the standard library, on none of the public headers.  Each library is one

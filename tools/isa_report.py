@@ -1,6 +1,6 @@
 """Static resource and instruction-class report of the compiled gfx950 kernels.
 
-    python tools/isa_report.py [--unit rtjpeg|dv|tga|spu|gsm][--kernel k_decode] [--cflags "..."] [--keep DIR] [--json] [--digest]
+    python tools/isa_report.py [--unit rtjpeg|dv|tga|spu|gsm|pcm][--kernel k_decode] [--cflags "..."] [--keep DIR] [--json] [--digest]
                                [--opcodes] [--src DIR] [--bodies FILE]
 
 Compiles csrc/mi_rtjpeg.hip (--unit dv: csrc/mi_dv.hip) with -save-temps (device assembly) and prints, per kernel, what the
@@ -32,7 +32,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 UNITS = {"rtjpeg": ("mi_rtjpeg", ["mi_rtjpeg.hip", "rtj_tables.cpp"]), "dv": ("mi_dv", ["mi_dv.hip", "dv_tables.cpp"]),
          "tga": ("mi_tga", ["mi_tga.hip"]), "spu": ("mi_spu", ["mi_spu.hip"]),
-         "gsm": ("mi_gsm", ["mi_gsm.hip"])}
+         "gsm": ("mi_gsm", ["mi_gsm.hip"]), "pcm": ("mi_pcm", ["mi_pcm.hip"])}
 
 
 def device_asm(cflags, keep=None, csrc=CSRC, unit="rtjpeg"):
